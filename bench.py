@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- MCTS simulations/sec of the batched self-play hot path on N MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
         no RANK/WORLD_SIZE in the environment (any N, 1 included): this process is a GPU-free LAUNCHER (as the reference's driver
-        spawns its own workers, transgo.py:92-107): it times the CPU baseline, starts N fresh child processes (one rank per GPU,
-        RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set), takes rank 0's JSON line and exits non-zero if any rank fails.  At N = 1
-        it then runs the SECONDARY legs -- the same workload under the opt-in split-precision network (`--dtype f32x3`) and under
-        the reference's shipped MainNetwork in exact f32 (`--network transgo`) -- each in a fresh child of its own, one after the
-        other, and prints ONE line: the exact-f32 tower as metric / value / dtype / config, the legs under "secondary".
+        spawns its own workers, transgo.py:92-107): it starts N fresh child processes (one rank per GPU, RANK / LOCAL_RANK /
+        WORLD_SIZE / MASTER_* set), takes rank 0's JSON line and exits non-zero if any rank fails.  A plain run measures the
+        headline only: set-up, stagger, W warm-up steps, K timed steps, the line.
+        --full adds everything else the benchmark measures: the CPU baseline legs (timed by the launcher before any rank starts)
+        and, at N = 1, the SECONDARY legs -- the same workload under the opt-in split-precision network (`--dtype f32x3`), under
+        the reference's shipped MainNetwork in exact f32 (`--network transgo`) and as four groups -- each in a fresh child of its
+        own, one after the other; still ONE line: the exact-f32 tower as metric / value / dtype / config, the legs under
+        "secondary".
+        --dump-outputs DIR: after the timed steps rank 0 writes what the last timed step delivered to the replay store -- the
+        sections of every finished-game batch (records.Harvest), concatenated in arrival order -- as DIR/<section>.npy in
+        float64 (integers, exact) or float32, at most 64 MB (beyond that a fixed seeded sample of whole games).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
-        (ranks started by somebody else: rank 0 times the CPU baseline before it touches the GPU, the others wait in
+        (ranks started by somebody else: with --full rank 0 times the CPU baseline before it touches the GPU, the others wait in
         init_process_group)
 
 Workload (BASELINE.json configs[1]): 9x9 Go, 400 simulations/move, 6-block x 128-filter tower (random-init weights),
@@ -166,6 +172,48 @@ def kernel_name(S, filters, dtype):
     return f"k_conv3x3<{S},{filters},{filters}> (fp32 MFMA 16x16x4 implicit GEMM)"
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(out_dir, batches, S, C, limit=DUMP_LIMIT_BYTES):
+    """Write the finished-game batches of the last timed step (records.Harvest, in the order the replay store received them) as
+    out_dir/<section>.npy, one file per section of records.layout, batches concatenated: per game n_moves, winner, slot, seed,
+    score, terr; per position obs_bits, counts, z, own, player.  Integer sections as float64 (exact), score and z as float32.
+    game_index.npy = each written game's index in that order.  Above `limit` bytes a fixed seeded sample of whole games (their
+    positions with them), in order."""
+    from transgo_amd import records
+    hs = [b.to_host() for b in batches]
+    per_game = ("n_moves", "winner", "slot", "seed", "score", "terr")
+    per_pos = ("obs_bits", "counts", "z", "own", "player")
+    sec0, _ = records.layout(S, C, 0, 0)
+    cat = {k: np.concatenate([h.view(k) for h in hs]) if hs else np.zeros(sec0[k][2], sec0[k][1]) for k in per_game + per_pos}
+    n_moves = cat["n_moves"].astype(np.int64)
+    ng = len(n_moves)
+    f32 = ("score", "z")
+
+    def row_bytes(names):
+        return sum((4 if k in f32 else 8) * int(np.prod(cat[k].shape[1:])) for k in names)
+    cost = row_bytes(per_game) + 8 + n_moves * row_bytes(per_pos)             # + 8: game_index
+    keep = np.arange(ng)
+    if cost.sum() > limit:
+        order = np.random.RandomState(DUMP_SAMPLE_SEED).permutation(ng)
+        keep = np.sort(order[np.cumsum(cost[order]) <= limit])
+    first = np.concatenate([[0], np.cumsum(n_moves)[:-1]]).astype(np.int64)
+    pos = np.concatenate([np.arange(first[g], first[g] + n_moves[g]) for g in keep]) if len(keep) else np.zeros(0, np.int64)
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"game_index": keep}
+    out.update({k: cat[k][keep] for k in per_game})
+    out.update({k: cat[k][pos] for k in per_pos})
+    total = 0
+    for k, v in out.items():
+        v = np.ascontiguousarray(v, np.float32 if k in f32 else np.float64)
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+        total += v.nbytes
+    print(f"bench.py: wrote {len(out)} arrays ({total / 2 ** 20:.1f} MiB; {len(keep)} of {ng} finished games of the last step, "
+          f"{len(pos)} positions) to {out_dir}", file=sys.stderr)
+
+
 def stagger(sp, period, sims=16):
     """Put slot g (g mod period) plies into its game -- slots with g mod period = 0 are never restarted and end up period - 1
     plies in -- by real self-play with cheap searches: `period - 1` untimed moves of every board, slot g restarted (fresh seed,
@@ -211,9 +259,15 @@ def parse_args(argv=None):
                     help="tree memory: 32-byte slots provisioned per game ON AVERAGE in the pool all boards of a GPU share (default: "
                          "(2*sims + 128) * (header + actions)); the line reports the pool's size, its high-water mark, how often it "
                          "ran empty and any truncated tree blocks, so a run can be sized for more boards per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: the CPU-baseline legs and, at N = 1, the secondary legs "
+                         "(off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the finished-game batches of the last timed step as DIR/<section>.npy "
+                         "(float64 / float32, at most 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=0.0,
-                    help="window of each CPU-baseline leg (default: 60 s at N = 1 as BASELINE.md 4 says, 30 s at N > 1)")
+                    help="with --full: window of each CPU-baseline leg (default: 60 s at N = 1 as BASELINE.md 4 says, 30 s at N > 1)")
     ap.add_argument("--cpu-json", default="", help="(set by the launcher) file holding the CPU-baseline legs the launcher timed")
     ap.add_argument("--launch-timeout", type=float, default=3000.0, help="launcher: seconds before the ranks are given up on")
     ap.add_argument("--no-launcher", action="store_true",
@@ -221,7 +275,7 @@ def parse_args(argv=None):
                          "needs (`rocprofv3 ... -- python3 bench.py --no-launcher --no-cpu-baseline`): its preloaded library has "
                          "initialised the GPU before Python starts, and such a process must not start GPU children")
     ap.add_argument("--secondary", choices=["auto", "none"], default="auto",
-                    help="auto: after the headline leg of the default family (N = 1, tower, f32, one group) the launcher times the "
+                    help="auto (with --full): after the headline leg of the default family (N = 1, tower, f32, one group) the launcher times the "
                          "f32x3 tower and the f32 MainNetwork on the same workload in fresh child processes and reports them under "
                          "\"secondary\" (never as `value`)")
     ap.add_argument("--secondary-timeout", type=float, default=240.0, help="launcher: seconds one secondary leg may take")
@@ -230,8 +284,8 @@ def parse_args(argv=None):
 
 def cpu_legs(a):
     """The two CPU-baseline legs (C2's net for the like-for-like ratio, C1 = the plumbing config beside it), run where no GPU
-    context exists: the launcher, or rank 0 before it touches the GPU."""
-    if a.no_cpu_baseline or a.board != 9 or a.network != "tower":
+    context exists: the launcher, or rank 0 before it touches the GPU.  Only with --full."""
+    if not a.full or a.no_cpu_baseline or a.board != 9 or a.network != "tower":
         return None, None
     secs = a.cpu_seconds if a.cpu_seconds > 0 else (60.0 if a.gpus <= 1 else 30.0)
     c2 = cpu_baseline(secs, a.sims, a.filters, a.blocks,
@@ -333,13 +387,27 @@ def _secondary_summary(line, wall_s):
             "leg_wall_s": round(wall_s, 1)}
 
 
+def _without_dump(argv):
+    """argv less --dump-outputs DIR / --dump-outputs=DIR (or an abbreviation argparse accepts, --du...)."""
+    out, skip = [], False
+    for x in argv:
+        name = x.split("=", 1)[0]
+        if skip:
+            skip = False
+        elif len(name) >= 4 and "--dump-outputs".startswith(name):
+            skip = "=" not in x
+        else:
+            out.append(x)
+    return out
+
+
 def launcher(a, argv):
     """`python bench.py --gpus N` with no rank environment: the GPU-free parent (nothing here imports torch or touches HIP).
-    CPU legs first, then N fresh children -- this same file with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set -- whose rank 0
-    writes the JSON line with the CPU legs merged in.  Any failing rank, or the join timeout, ends the others (exact PIDs) and
-    the launcher exits non-zero.  At N = 1 the secondary legs follow, each in its own fresh child (never an exec, never a second
-    network inside a process that already holds one): a leg that fails leaves {"error": ...} under its name and does not take
-    the headline with it."""
+    CPU legs first (--full only), then N fresh children -- this same file with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set --
+    whose rank 0 writes the JSON line with the CPU legs merged in.  Any failing rank, or the join timeout, ends the others (exact
+    PIDs) and the launcher exits non-zero.  With --full at N = 1 the secondary legs follow, each in its own fresh child (never an
+    exec, never a second network inside a process that already holds one): a leg that fails leaves {"error": ...} under its name
+    and does not take the headline with it."""
     import tempfile
     cpu, cpu_c1 = cpu_legs(a)
     tmp = tempfile.mkdtemp(prefix="transgo_bench_")
@@ -358,11 +426,12 @@ def launcher(a, argv):
         print("bench.py launcher: rank 0 printed no result line", file=sys.stderr)
         return 1
     line["launcher_wall_s"] = {"cpu_legs_and_headline": round(time.time() - t0, 1)}
-    if a.gpus == 1 and a.secondary == "auto" and (a.dtype, a.network, a.groups) == ("f32", "tower", 1):
+    if a.full and a.gpus == 1 and a.secondary == "auto" and (a.dtype, a.network, a.groups) == ("f32", "tower", 1):
         sec = {}
+        base = _without_dump(argv)                                          # the headline's outputs are the ones dumped
         for name, extra, max_steps, max_warm in SECONDARY_LEGS:
-            leg = [x for x in argv] + extra + ["--steps", str(min(a.steps, max_steps)), "--warmup", str(min(a.warmup, max_warm)),
-                                               "--no-cpu-baseline"]
+            leg = base + extra + ["--steps", str(min(a.steps, max_steps)), "--warmup", str(min(a.warmup, max_warm)),
+                                  "--no-cpu-baseline"]
             t1 = time.time()
             rc2, txt2, why2 = _spawn_ranks(leg, 1, tmp, name, a.secondary_timeout)
             l2 = _result_line(txt2)
@@ -492,12 +561,15 @@ def main(argv=None):
             torch.cuda.synchronize()
 
     tally = {"games": 0, "positions": 0}
+    last_batches = []                                                     # what the latest step handed to the replay store
 
     def one_step():
+        last_batches.clear()
         hs = sp.advance(device=True)
         for h in (hs if a.groups > 1 else [hs]):                          # one gather per group, the same number on every rank
             for hb in gather_harvest(h, S, 10, dst=0, device_index=gpu):  # rank 0: every rank's finished games
                 mem.append_harvest(hb)
+                last_batches.append(hb)
                 tally["games"] += hb.n_games; tally["positions"] += hb.n_positions
 
     for _ in range(a.warmup):
@@ -584,6 +656,8 @@ def main(argv=None):
     ranks["seeds_disjoint"] = bool(len(np.unique(cat)) == len(cat))       # no two running games of the job share an RNG stream
     ranks["transport"] = transport_name() if world > 1 else "none (one rank: finished games go device -> device into the store)"
 
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, last_batches, S, 10)
     if rank == 0:
         # HBM bytes per launch of the dominant kernel come from PMC passes (separate rocprofv3 runs, committed under profiles/);
         # they describe one configuration AND one build: the file records the hash of net.hip it was collected on, and a figure
@@ -618,7 +692,7 @@ def main(argv=None):
         line = {
             "metric": "REHEARSAL with a stand-in engine (not MCTS simulations/sec)" if standin else "MCTS simulations/sec",
             "value": round(value, 1), "unit": "stand-in steps/s" if standin else "sims/s", "n_gpus": world,
-            "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 2),
+            "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype,
             "data": "stand-in engine (CPU rehearsal of the N-rank control flow: NOT a measurement)" if standin else "synthetic",
             "games_per_hour": round(games_stored / dt * 3600.0, 1),

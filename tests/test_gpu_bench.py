@@ -1,5 +1,5 @@
 """bench.py as the driver runs it.  `python bench.py --gpus N` with N > 1 and no rank environment is a LAUNCHER: a GPU-free parent
-that times the CPU baseline, starts N ranks of its own and forwards rank 0's line (the reference's driver
+that (with --full) times the CPU baseline, starts N ranks of its own and forwards rank 0's line (the reference's driver
 spawns its workers itself, transgo.py:92-107).  On the one-GPU box the two ranks share the card and gloo carries the collectives."""
 import json
 import os
@@ -22,7 +22,7 @@ def _run(args, timeout, **env):
 
 
 def test_bench_launches_its_own_two_ranks():
-    r = _run("--gpus 2 --games 1024 --steps 3 --warmup 1".split(), 900, TRANSGO_DIST_BACKEND="gloo")
+    r = _run("--gpus 2 --games 1024 --steps 3 --warmup 1 --full".split(), 900, TRANSGO_DIST_BACKEND="gloo")
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -67,9 +67,9 @@ def test_bench_rehearses_more_than_two_ranks():
 
 
 def test_bench_one_gpu_line_carries_the_secondary_legs():
-    """`python bench.py --gpus 1` is the same launcher: headline leg (exact-f32 tower) in a fresh child, then the f32x3 tower and the
-    f32 MainNetwork on the same workload in fresh children of their own, ONE line (tiny sizes here)."""
-    r = _run("--gpus 1 --games 256 --sims 32 --steps 2 --warmup 1 --stagger 8 --cpu-seconds 3".split(), 900)
+    """`python bench.py --gpus 1 --full` is the same launcher: headline leg (exact-f32 tower) in a fresh child, then the f32x3 tower
+    and the f32 MainNetwork on the same workload in fresh children of their own, ONE line (tiny sizes here)."""
+    r = _run("--gpus 1 --games 256 --sims 32 --steps 2 --warmup 1 --stagger 8 --cpu-seconds 3 --full".split(), 900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

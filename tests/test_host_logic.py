@@ -565,3 +565,61 @@ def test_bench_launcher_world8_rehearsal_with_the_stand_in_engine():
     assert r2.returncode == 0, r2.stderr[-3000:]
     l2 = json.loads([l for l in r2.stdout.splitlines() if l.startswith("{")][0])
     assert "isend/irecv" in l2["ranks"]["transport"] and l2["selfplay_games"]["positions_stored"] == sg["positions_stored"]
+
+
+def test_bench_plain_run_and_dump_outputs_with_the_stand_in_engine(tmp_path):
+    """A plain `bench.py` run times the headline only (no CPU legs, no secondary legs: those are --full), `--steps` is the number of
+    timed steps, and `--dump-outputs DIR` writes the batches the last timed step handed to the replay store: every rank's finished
+    games in rank order, integer sections exact in float64, the same files from run to run."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "TRANSGO_GATHER")}
+    env.update(TRANSGO_BENCH_STANDIN="1", TRANSGO_DIST_BACKEND="gloo")
+    dumps = []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + f"--gpus 2 --games 32 --steps 2 --warmup 1 --dump-outputs {d}".split(),
+                           cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert line["cpu_baseline"] is None and line["cpu_baseline_c1"] is None and "secondary" not in line
+        assert [p["games_finished"] for p in line["ranks"]["per_rank"]] == [2 * 1, 2 * 2]       # stand-in: 1 + rank % 3 per step
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    a, b = dumps
+    assert sorted(a) == sorted(b) == sorted(["game_index", "n_moves", "winner", "slot", "seed", "score", "terr", "obs_bits", "counts",
+                                             "z", "own", "player"])
+    for k in a:
+        assert a[k].dtype == (np.float32 if k in ("score", "z") else np.float64) and np.array_equal(a[k], b[k]), k
+    # the last step's games: one from rank 0 (2 plies), two from rank 1 (3 plies each)
+    assert list(a["n_moves"]) == [2, 3, 3] and list(a["game_index"]) == [0, 1, 2]
+    assert a["counts"].shape == (8, 82) and a["obs_bits"].shape == (8, 26) and a["own"].shape == (8, 81) and a["terr"].shape == (3, 81)
+    assert (a["counts"][:, 5] == 7).all() and set(np.unique(a["z"])) <= {-1.0, 1.0}
+
+
+def test_bench_dump_outputs_samples_whole_games_beyond_the_limit(tmp_path):
+    import bench
+    from tests.bench_standin import StandInSelfPlay
+
+    class C:
+        board_size = 9
+    hs = [StandInSelfPlay(C(), 16, rank=r, world=4).advance() for r in range(4)]
+    full, part = str(tmp_path / "full"), str(tmp_path / "part")
+    bench.dump_outputs(full, hs, 9, 10)
+    bench.dump_outputs(part, hs, 9, 10, limit=20000)
+    A = {f[:-4]: np.load(os.path.join(full, f)) for f in os.listdir(full)}
+    P = {f[:-4]: np.load(os.path.join(part, f)) for f in os.listdir(part)}
+    assert sum(v.nbytes for v in P.values()) <= 20000 < sum(v.nbytes for v in A.values())
+    assert list(A["game_index"]) == list(range(7)) and 0 < len(P["game_index"]) < 7
+    keep = P["game_index"].astype(int)
+    assert list(keep) == sorted(keep)
+    first = np.concatenate([[0], np.cumsum(A["n_moves"])[:-1]]).astype(int)
+    rows = np.concatenate([np.arange(first[g], first[g] + int(A["n_moves"][g])) for g in keep])
+    for k in ("n_moves", "winner", "seed", "score", "terr"):
+        assert np.array_equal(P[k], A[k][keep]), k
+    for k in ("obs_bits", "counts", "z", "own", "player"):
+        assert np.array_equal(P[k], A[k][rows]), k

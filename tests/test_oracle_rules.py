@@ -5,12 +5,9 @@ moves left unchanged, stepping a finished game)."""
 import os
 
 import numpy as np
-import pytest
 
 from oracle.go_oracle import OracleGoEnv
 from tests import rules_replay
-
-HAVE_REF = os.path.exists("/root/reference/GoEnv/cpp_src/board.cc")
 
 
 def test_rules_fixture(golden_dir):
@@ -45,45 +42,32 @@ def test_max_step_cutoff():
     assert done and env.isTerminated(s)
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference tree only exists in the build container")
-def test_against_compiled_reference_19x19_logic_is_size_generic():
-    """Size-generic code paths: the same oracle binary at S=9 equals the compiled reference on fresh random games
-    (not the fixture seeds)."""
-    import ctypes
-    so = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "GoEnv", "go_env.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref not built")
-    lib = ctypes.CDLL(so)
-    lib.Init.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float]
-    lib.Init(1, 10, 120, 7.5)
-    lib.Step.restype = ctypes.c_bool
-    lib.getScore.restype = ctypes.c_float
-    lib.checkAction.restype = ctypes.c_bool; lib.isTerminated.restype = ctypes.c_bool
+def test_against_compiled_reference_19x19_logic_is_size_generic(golden_dir):
+    """Size-generic code paths: the same oracle binary at S=9 equals the compiled reference on 40 more random games (not the
+    rules fixture's seeds), recorded ply by ply from the reference's C ABI in tests/golden/compiled_ref_s9.npz
+    (tests/golden/gen_compiled_ref.py)."""
+    with np.load(os.path.join(golden_dir, "compiled_ref_s9.npz")) as z:
+        rec = {k.split("/", 1)[1]: z[k] for k in z.files if k.startswith("generic/")}
     env = OracleGoEnv()
-    rng = np.random.RandomState(99)
-    for g in range(40):
-        a = ctypes.create_string_buffer(1200); lib.Reset(a)
-        b, _ = env.reset()
-        done = False
-        while not done:
-            buf = (ctypes.c_int * 82)()
-            n = lib.getLegalAction(a, buf)
-            la = list(buf[:n]); la = la if n == 1 else la[:-1]
-            assert la == [int(x) for x in env.getLegalAction(b)]
-            e = np.zeros(810, np.float32); lib.Encode(a, e.ctypes.data_as(ctypes.c_void_p))
-            assert (e == env.encode(b).reshape(-1)).all()
-            assert lib.getScore(a) == env.getScore(b)
-            if env.getStep(b) % 16 == 1:                 # the reference prints a line for every refusal: sample, do not flood
-                for c in (81, -1, -2):                   # S*S is NOT translated to PASS here (only Step does that); -1 / -2 are
-                    assert bool(lib.checkAction(a, ctypes.c_int(c))) == bool(env.checkAction(b, c)), c
-            assert bool(lib.isTerminated(a)) == bool(env.isTerminated(b))
-            assert (lib.getPlayer(a) & 0xFF) == env.getPlayer(b) and lib.getStep(a) == env.getStep(b)
-            act = la[rng.randint(len(la))] if rng.rand() > 0.04 else 81
-            a2 = ctypes.create_string_buffer(1200)
-            d1 = lib.Step(a, a2, ctypes.c_int(act)); a = a2
-            b, d2 = env.step(b, act)
-            assert bool(d1) == d2
-            done = d2
+    game, off = rec["game"], rec["legal_off"]
+    assert len(np.unique(game)) == 40
+    b = None
+    for i in range(len(game)):
+        if i == 0 or game[i] != game[i - 1]:
+            b, _ = env.reset()
+        la = [int(x) for x in rec["legal"][off[i]:off[i + 1]]]
+        assert la == [int(x) for x in env.getLegalAction(b)], i
+        assert (rec["enc"][i] == env.encode(b).reshape(-1)).all(), i
+        assert rec["score"][i] == env.getScore(b), i
+        if env.getStep(b) % 16 == 1:                     # the reference prints a line for every refusal: sampled, not flooded
+            assert (rec["check"][i] >= 0).all()
+            for c, want in zip((81, -1, -2), rec["check"][i]):   # S*S is NOT translated to PASS here (only Step does that)
+                assert bool(want) == bool(env.checkAction(b, c)), (i, c)
+        assert bool(rec["terminated"][i]) == bool(env.isTerminated(b)), i
+        assert rec["player"][i] == env.getPlayer(b) and rec["step"][i] == env.getStep(b), i
+        b, d2 = env.step(b, int(rec["action"][i]))
+        assert bool(rec["done"][i]) == d2, i
+        assert d2 == (i + 1 == len(game) or game[i + 1] != game[i]), i
 
 
 def test_rules_fixture_19x19(golden_dir):
