@@ -33,6 +33,23 @@ struct AttW { ConvW qkv; const float* gamma; const float* s; const float* t;    
               const _Float16* x3w = nullptr; const float* x3sc = nullptr; };          // split q|k|v weights (LDS image) + 2^-s of k_attention_x3
 struct Layer { int kind; int ridx; AttW a; };                                         // kind 0: residual block blocks[ridx]; 1: attention
 
+// Which forward runs, decided once at load (net_path) and read by the buffer allocation, the weight restaging and forward_t.
+//   CHAIN_F32   general f32 chain: k_conv3x3 everywhere (F = 32 / 64, 19x19 attention archs, TG_DMA_CONV=0, and the DMA
+//               chain's batches of 2 GiB or more per activation buffer)
+//   CHAIN_DMA   f32 tower of 128 / 256 filters on the DMA-fed k_conv3x3_sg; every producer also writes relu(bn1_next(.))
+//               slice-major for a residual block that follows, so the F->F kernels never activate anything
+//   CHAIN_F16   fp16 storage, f32 accumulate (k_conv3x3_h2; stem and head conv too); the residual stream stays f32 unless r16
+//   CHAIN_SPLIT split precision ("f32x3"): every conv operand as fp16 hi + lo, three of the four products on the fp16 MFMA; the
+//               residual stream, the dense heads and (beyond the fused k_attention_x3) attention stay f32
+enum Chain { CHAIN_F32 = 0, CHAIN_DMA, CHAIN_F16, CHAIN_SPLIT };
+struct NetPath {
+    Chain chain = CHAIN_F32;
+    bool r16 = false;          // CHAIN_F16: fp16 residual stream too (net_precision 2)
+    bool att_x3 = false;       // CHAIN_SPLIT: attention blocks on the fused k_attention_x3 (9x9, F = 128)
+    bool head_x2 = false;      // CHAIN_SPLIT: the head conv on k_head_gemm_x2 (F = 128, the trunk ends in a residual block)
+    size_t att_lds = 0;        // k_attention's dynamic LDS in bytes; 0: no attention, or its image does not fit
+};
+
 struct Net {
     int F = 0, NB = 0, C = 0, S = 0, P = 0, A = 0;
     float* blob = nullptr; size_t blob_floats = 0;
@@ -49,7 +66,7 @@ struct Net {
     float* wsc = nullptr;                          // prec 3: [2*NB + 1] power-of-two factor 2^-s each conv's weights were scaled by before splitting (stem last)
     _Float16* stem_h = nullptr; _Float16* head_h = nullptr; _Float16* x0h = nullptr;   // fp16 path: stem [2*9][F][32] (16 planes padded to 64), head [F/32*9][16][32], input [rows][P][64]
     _Float16* wh = nullptr; _Float16* act16 = nullptr; _Float16* h16 = nullptr;   // fp16 path: weights [2*NB][F/32*9][F][32], activations [rows][P][F]
-    int dma = 0;                                   // attention-free F=128/256 f32 tower: 1 = k_conv3x3_sg chain (default), 0 = k_conv3x3 (TG_DMA_CONV=0)
+    NetPath path;
     ConvW head; const float* w_vo = nullptr; const float* b_vo = nullptr; const float* w_v = nullptr; const float* b_v = nullptr;
     const float* w_o = nullptr; const float* b_o = nullptr; const float* w_a = nullptr; const float* b_a = nullptr;
     // engine batches arrive bit-packed and sparse (engine.h: obs_bits through row_slot); tg_net_predict hands float planes
@@ -354,24 +371,8 @@ __device__ __forceinline__ void tg_dma_buffer(u32x4 rsrc, int voff_bytes, tg_lds
 // conflicted on every read (measured: SQ_LDS_BANK_CONFLICT = 49 % of SQ_LDS_IDX_ACTIVE).
 __device__ __forceinline__ int swz64(int row) { return ((row >> 2) & 1) << 1; }
 
-#ifndef TG_H2_XCD
-#define TG_H2_XCD 0        // experiment switch: XCD-contiguous row-tile order in k_conv3x3_h2
-#endif
-#ifndef TG_X2_3P
-#define TG_X2_3P 1         // split precision: three partial products per stage pair (0: all four)
-#endif
-#ifndef TG_SG_PERSIST128
-#define TG_SG_PERSIST128 0
-#endif
-#ifndef TG_SG_XCD
-#define TG_SG_XCD 1        // XCD-contiguous tile order in k_conv3x3_sg (F = 128): HBM reads 1.21x -> 1.12x (EPI 0) / 1.10x -> 1.05x (EPI 1) of the input bytes, time unchanged; 0 = linear order
-#endif
-#ifndef TG_SG_PRIO
-#define TG_SG_PRIO 0       // experiment switch: wave priority around the MFMA cluster (1), the epilogue (2), the weight-DMA issue (4)
-#endif
-#ifndef TG_SG_NG
-#define TG_SG_NG 2           // k_conv3x3_sg at F=128: stages per barrier (ring = 2*NG slots of 8 KB); measured 2: 138.5, 3: 131.6, 4: 127.1 TFLOP/s
-#endif
+// k_conv3x3_sg at F=128: stages per barrier (ring = 2*NG slots of 8 KB); measured 2: 138.5, 3: 131.6, 4: 127.1 TFLOP/s
+constexpr int kSgStagesPerBarrier = 2;
 // ---- F->F 3x3 conv of the f32 tower (F = 128 / 256, attention-free; input already activated by its producer) -------------------
 // Implicit GEMM on v_mfma_f32_16x16x4_f32: D[cout][pos] += W[tap][cout][cin] * X[pos + tap][cin].  F = 128: workgroup = 4 waves =
 // 192 consecutive rows x all 128 couts (wave: 3 position x 8 cout tiles, 96 accumulator registers), <= 162 VGPRs and 34 KB of LDS,
@@ -398,7 +399,7 @@ __global__ __launch_bounds__(256, (F == 128 ? (NPT_ == 3 ? 3 : 4) : 2)) void k_c
     constexpr int P = S * S, CT = F / 16, CC = 16;
     constexpr int NPT = NPT_, TM = 64 * NPT;
     constexpr int WPW = CT / 4;
-    constexpr int NSL = F / CC, NST = NSL * 9, NG = TG_SG_NG, D = F == 128 ? 2 * NG : 4, NGS = D / 2, NGRP = NST / NGS;   // NGS stages per barrier, two groups resident
+    constexpr int NSL = F / CC, NST = NSL * 9, NG = kSgStagesPerBarrier, D = F == 128 ? 2 * NG : 4, NGS = D / 2, NGRP = NST / NGS;   // NGS stages per barrier, two groups resident
     static_assert((F == 128 || F == 256) && NST % NGS == 0, "tile geometry");
     __shared__ __attribute__((aligned(16))) float ws[D][F * CC];
     __shared__ __attribute__((aligned(16))) float par[3 * F];
@@ -408,10 +409,11 @@ __global__ __launch_bounds__(256, (F == 128 ? (NPT_ == 3 ? 3 : 4) : 2)) void k_c
     const int j = lane & 15, kq = lane >> 4;
     // XCD-aware tile order (one tile per workgroup, F = 128): workgroup b runs on XCD b % 8, so XCD x takes the CONTIGUOUS tile range
     // [x * tpx, (x + 1) * tpx) -- neighbouring tiles share their halo rows through one L2 instead of fetching them into two
+    // (HBM reads 1.21x -> 1.12x (EPI 0) / 1.10x -> 1.05x (EPI 1) of the input bytes, time unchanged)
     int bid = blockIdx.x;
-    if (TG_SG_XCD && !(F == 256 || TG_SG_PERSIST128)) { const int tpx = ((int)gridDim.x + 7) >> 3; bid = (bid & 7) * tpx + (bid >> 3); }
+    if (F == 128) { const int tpx = ((int)gridDim.x + 7) >> 3; bid = (bid & 7) * tpx + (bid >> 3); }
     int m0 = bid * TM;
-    if (TG_SG_XCD && m0 >= M) return;                                   // the grid is rounded up to a multiple of 8
+    if (m0 >= M) return;                                                // the grid is rounded up to a multiple of 8
     for (int i = tid; i < F; i += 256) { par[i] = bias[i]; par[F + i] = out2 ? s2[i] : 0.f; par[2 * F + i] = out2 ? t2[i] : 0.f; }
 
     const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, M * F * 4, 0x00020000);
@@ -428,7 +430,7 @@ __global__ __launch_bounds__(256, (F == 128 ? (NPT_ == 3 ? 3 : 4) : 2)) void k_c
     // barriers), so the dispatcher-like balance is kept while the next tile's first weights go out before the current tile's stores
     // and its residual / first B fragments right after them (+1.2-1.7 %).  At F = 128 (shorter tiles, three workgroups per CU) the
     // same loop costs 2 %, so there every workgroup takes exactly one tile.
-    constexpr bool PERSIST = F == 256 || TG_SG_PERSIST128;
+    constexpr bool PERSIST = F == 256;
     const int ntiles = (M + TM - 1) / TM;
     const int aoff = j * CC + ((kq ^ swz64(j)) << 2);
     unsigned vmask[NPT]; int boff[NPT];
@@ -485,9 +487,6 @@ __global__ __launch_bounds__(256, (F == 128 ? (NPT_ == 3 ? 3 : 4) : 2)) void k_c
                 const float* wcur = ws[g % D];
                 if (g + 1 < NST) load_b(b_next, g + 1);
                 __builtin_amdgcn_sched_barrier(0);                       // keep the loads HERE: hipcc sinks them to their use, a stage later
-#if TG_SG_PRIO & 1
-                __builtin_amdgcn_s_setprio(1);
-#endif
                 f32x4 a_cur = *reinterpret_cast<const f32x4*>(wcur + aoff);
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct) {
@@ -500,23 +499,14 @@ __global__ __launch_bounds__(256, (F == 128 ? (NPT_ == 3 ? 3 : 4) : 2)) void k_c
                             acc[ct][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[s4], b_cur[t][s4], acc[ct][t], 0, 0, 0);
                     a_cur = a_next;
                 }
-#if TG_SG_PRIO & 1
-                __builtin_amdgcn_s_setprio(0);
-#endif
                 TG_VMCNT(0);                                             // B fragments of stage g+1 (and any weight pieces): a stage old
 #pragma unroll
                 for (int t = 0; t < NPT; ++t) b_cur[t] = b_next[t];
             }
             TG_BARRIER();                                                // group pp+1 has landed for everybody; the slots of group pp are free
             if (NGS * (pp + 2) < NST) {
-#if TG_SG_PRIO & 4
-                __builtin_amdgcn_s_setprio(2);
-#endif
 #pragma unroll
                 for (int h = 0; h < NGS; ++h) dma_w(NGS * (pp + 2) + h);
-#if TG_SG_PRIO & 4
-                __builtin_amdgcn_s_setprio(0);
-#endif
             }
         }
         int mrow[NPT];
@@ -528,13 +518,7 @@ __global__ __launch_bounds__(256, (F == 128 ? (NPT_ == 3 ? 3 : 4) : 2)) void k_c
 #pragma unroll
             for (int g = 0; g < D; ++g) dma_w(g);
         }
-#if TG_SG_PRIO & 2
-        __builtin_amdgcn_s_setprio(3);
-#endif
         conv_epilogue<F, CT, NPT, (EPI == 1 ? 2 : EPI), EPI == 0, true>(acc, mrow, M, 0, kq, out, res, out2, par);
-#if TG_SG_PRIO & 2
-        __builtin_amdgcn_s_setprio(0);
-#endif
         if (!more) break;
         m0 = next * TM;
         tile_setup();
@@ -672,8 +656,8 @@ __device__ __forceinline__ void conv_epilogue_h8(f32x4 (&acc)[CT][NPT], const in
 // accumulation from ONE read of the activations and two reads of the SAME weight tile (lane (j, kq) takes 16-B chunk kq & 1 of
 // row j for the hi fragment, 2 + (kq & 1) for the lo one -- no duplicate storage, the swizzle and its conflict-freedom carry
 // over).  4 x the MFMA work of the plain fp16 conv at ~22 significand bits per operand, against 16 x for the exact-f32 MFMA.
-// With TG_X2_3P (default) only THREE of the four products are formed -- w_lo*a_lo is dropped and the two lo-weight products of a
-// pair of stages share one K = 32 step (see the stage loop): 3 x the MFMA work of the plain fp16 conv.
+// Only THREE of the four products are formed -- w_lo*a_lo is dropped and the two lo-weight products of a pair of stages share one
+// K = 32 step (see the stage loop): 3 x the MFMA work of the plain fp16 conv.
 template <int S, int CIN, int F, int EPI, bool R16 = false, bool X2 = false>
 __global__ __launch_bounds__(256, 2) void k_conv3x3_h2(const _Float16* __restrict__ in, float* __restrict__ out32,
                                                        _Float16* __restrict__ out16, const float* __restrict__ res,
@@ -699,10 +683,8 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_h2(const _Float16* __restric
     // the COS cout parts of one row tile are blocks b and b+8: same XCD (b % 8), dispatched together, so the slab's second read hits L2
     // Persistent: this workgroup takes blocks bid, bid + gridDim.x, ... (gridDim.x is a multiple of 8*COS, so the cout part co0
     // never changes); blocks whose rows lie past M (the block count is rounded up) are skipped.
-    // TG_H2_XCD: XCD x (= b % 8) takes the contiguous row-tile range [x * tpx, (x + 1) * tpx), tpx = nblk / (8 * COS), so neighbouring
-    // tiles share their slab halos through one L2 (linear order: consecutive tiles sit on consecutive XCDs and every halo is fetched twice)
     auto tile_m0 = [&](int b) {
-        if (TG_H2_XCD) return ((b % 8) * (nblk / (8 * COS)) + b / (8 * COS)) * TM;
+        (void)nblk;                                                     // captured: keeps the tile walk's code as measured
         return (COS == 1 ? b : (b / (8 * COS)) * 8 + b % 8) * TM;
     };
     int bid = blockIdx.x;
@@ -824,7 +806,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_h2(const _Float16* __restric
 #pragma unroll 1                                                         // unrolled, hipcc keeps 4 pairs of address state live and spills
         for (int pp = 0; pp < NPAIR; ++pp) {
           const int g0 = 2 * pp;
-          if constexpr (X2 && TG_X2_3P) {
+          if constexpr (X2) {
             // THREE partial products per pair of stages instead of four: w_lo * a_lo (2^-22 of a product, below the f32 rounding of the
             // sum) is dropped.  Steps of a pair (s0, s1 = its two stages, same or neighbouring slice, both tiles in the ring):
             //   CT steps  [w_hi(s0) | w_hi(s0)] x [a_hi(s0) | a_lo(s0)]      (as before)
@@ -868,14 +850,10 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_h2(const _Float16* __restric
 #pragma unroll
             for (int t = 0; t < NPT; ++t) b_cur[t] = b_next[t];
           } else {
-            constexpr int SPS = X2 ? 2 * CT : CT;                        // MFMA steps per stage (X2: hi and lo fragment of every cout tile)
+            constexpr int SPS = CT;                                      // MFMA steps per stage
             constexpr int NU = 2 * SPS, DA = 4;
             // A fragments run DA-1 steps ahead of their MFMAs (a step = 4 MFMAs = 64 cycles; an LDS read under load takes longer)
-            auto a_addr = [&](int un) -> const _Float16* {
-                const int st = un / SPS, w = un % SPS;
-                const int ct = X2 ? w >> 1 : w;
-                return ws[(g0 + st) % NSLOT] + ct * 16 * KC + ((X2 && (w & 1)) ? aoff_lo : aoff);
-            };
+            auto a_addr = [&](int un) -> const _Float16* { return ws[(g0 + un / SPS) % NSLOT] + (un % SPS) * 16 * KC + aoff; };
             f32x4 a[DA];
 #pragma unroll
             for (int u = 0; u < DA - 1; ++u) a[u] = *reinterpret_cast<const f32x4*>(a_addr(u));
@@ -883,7 +861,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_h2(const _Float16* __restric
             for (int u = 0; u < NU; ++u) {
                 if (u + DA - 1 < NU) a[(u + DA - 1) % DA] = *reinterpret_cast<const f32x4*>(a_addr(u + DA - 1));
                 if (u % SPS == SPS / 2 && g0 + u / SPS + 1 < NST) read_b(b_next, g0 + u / SPS + 1);   // that stage's slab is visible (see below)
-                const int ct = X2 ? (u % SPS) >> 1 : u % SPS;
+                const int ct = u % SPS;
 #pragma unroll
                 for (int t = 0; t < NPT; ++t)
                     acc[ct][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a[u % DA]), __builtin_bit_cast(h8, b_cur[t]),
@@ -1419,12 +1397,9 @@ __device__ __forceinline__ float row16_step(float v, int step) {
 //   DMA-fed chain, also as its pre-activated slice-major input relu(bn1_next(y)) (out2).
 // MFMA work per board: 288 + 1008 instructions of 16x16x4 (F = 128) = 1.3 % of an F->F conv's; the scalar-FMA kernel above took
 // 8.3 ms per 16384 boards (3 x an F->F conv), this one is bounded by its 97 KB of q/k/v/x/y traffic per board.
-#ifndef TG_ATT_OCC
-#define TG_ATT_OCC 1
-#endif
 // X2O: out2 is the split-precision chain's conv input instead -- fp16 hi + lo of relu(bn1_next(y)), chunk-major (x2_index).
 template <int S, int F, int CP, bool X2O = false>
-__global__ __launch_bounds__(256, TG_ATT_OCC) void k_attention_mfma(const float* __restrict__ qkv, const float* __restrict__ xin,
+__global__ __launch_bounds__(256, 1) void k_attention_mfma(const float* __restrict__ qkv, const float* __restrict__ xin,
                                                         float* __restrict__ out, float* __restrict__ out2,
                                                         const float* __restrict__ gamma, const float* __restrict__ bs,
                                                         const float* __restrict__ bt, const float* __restrict__ ps,
@@ -1614,18 +1589,10 @@ __global__ __launch_bounds__(256, TG_ATT_OCC) void k_attention_mfma(const float*
 //     were touched towards L2 (LDS-DMA into a scratch KB) at the start of phase B.
 // Per board: 1152 K=32 fp16 steps (projection) + 1296 f32 16x16x4 steps (exact-f32 energy and output GEMMs) = 59 k cycles of MFMA;
 // measured 130 k cycles per board (0.98 ms per 16 k boards; MFMA pipe 40 % busy).  PRO: x is relu(x*ps + pt) first (attention in
-// the policy head, model.py:94,106).  Diagnostics: -DTG_ATT_STAMP (phase stamps, scripts/stamp_att.py), TG_ATT_X3=0 (the two-kernel
-// form), -DTG_ATT_TOUCH=0, -DTG_ATT_IGLP=0.
-#ifndef TG_ATT_IGLP
-#define TG_ATT_IGLP 1
-#endif
-#if TG_ATT_IGLP
+// the policy head, model.py:94,106).  Diagnostics: -DTG_ATT_STAMP (phase stamps, scripts/stamp_att.py).
 // NM MFMAs with KV VALU instructions (the split of the next group) in the shadow of each
 #define TG_ATT_SCHED(NM, KV) do { _Pragma("unroll") for (int i_ = 0; i_ < (NM); ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); \
                                   __builtin_amdgcn_sched_group_barrier(0x002, (KV), 0); } __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define TG_ATT_SCHED(NM, KV) __builtin_amdgcn_sched_barrier(0)
-#endif
 #ifdef TG_ATT_STAMP
 // diagnostic build: phase stamps (s_memtime, 100 MHz) of the third board of wave 0 of workgroup 0, PRO = false launches
 __device__ unsigned long long g_att_stamp[32];
@@ -1633,12 +1600,6 @@ __device__ unsigned long long g_att_stamp[32];
                           __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
 #define TG_ASTAMP(i) do { } while (0)
-#endif
-#ifndef TG_ATT_TOUCH
-#define TG_ATT_TOUCH 1
-#endif
-#ifndef TG_ATT_RESID_PERM
-#define TG_ATT_RESID_PERM 1
 #endif
 template <int S, int F, bool PRO>
 __global__ __launch_bounds__(256, 1) void k_attention_x3(const float* __restrict__ xin, float* __restrict__ out, _Float16* __restrict__ out2,
@@ -1677,12 +1638,11 @@ __global__ __launch_bounds__(256, 1) void k_attention_x3(const float* __restrict
     const float wsc = wsc_p[0];
     const int M = rows * P;
     // Addresses: tile t of a board starts 16 rows = 16*F floats further (a scalar add on the board pointer); within the tile lane j
-    // takes row j -- except in the last tile, where rows past the board clamp to its last row.  Four per-lane byte offsets serve
-    // every access: {first five tiles, last tile} x {8-channel column of the projection reads, 4-channel column of the D tiles}.
+    // takes row j -- except in the last tile, where rows past the board clamp to its last row.  Three per-lane byte offsets serve
+    // every access: {first five tiles, last tile} x the 8-channel column of the projection reads, and the 4-channel column of the D tiles.
     constexpr int LASTR = P - 1 - (NT - 1) * 16;                                     // last valid row of the last tile
     const unsigned rowA = (unsigned)j * F * 4u, rowB = (unsigned)(j <= LASTR ? j : LASTR) * F * 4u;
     const unsigned xoA = rowA + chx * 4u, xoB = rowB + chx * 4u, eoA = rowA + kq * 16u;
-    [[maybe_unused]] const unsigned eoB = rowB + kq * 16u;
     const unsigned hoA = ((unsigned)(kq >> 1) * M + j) * 16u + (kq & 1) * 8u;        // split chunk-major output, + t*256 per tile
     auto tile = [](const float* board, int t) { return board + t * 16 * F; };
     auto ld16 = [](const float* base, unsigned byte_off) { return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + byte_off); };
@@ -1815,14 +1775,12 @@ __global__ __launch_bounds__(256, 1) void k_attention_x3(const float* __restrict
         // its loads run only one group ahead of their use -- from HBM that was 17 % of a board's time
         const int bnx = b + gridDim.x * 4;
         const float* const xnext = xin + (size_t)(bnx < rows ? bnx : b) * P * F;
-#if TG_ATT_TOUCH
         // as LDS-DMA into a scratch KB of this wave: no destination registers, nothing ever waits for them
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
             const unsigned lo = (unsigned)(lane + 64 * i) * 128u, off = lo < (unsigned)(P * F * 4 - 16) ? lo : (unsigned)(P * F * 4 - 16);
             tg_dma_global(xnext, (int)off, (tg_lds_void*)(&att_smem[(size_t)NG * W * 64 + (W + 6 * F) * 4 + wave * 1024]));
         }
-#endif
         __builtin_amdgcn_sched_barrier(0);
         TG_ASTAMP(27);
 #pragma unroll
@@ -1850,27 +1808,24 @@ __global__ __launch_bounds__(256, 1) void k_attention_x3(const float* __restrict
                     if (hg + 1 < 2 * NG) wf[ct] = wslot(hg + 1, ct);
                 }
                 if ((hg & 1) == 0 && hg + 2 < 2 * NG) xfn = split8(rv[hg / 2 + 1], pro_of(hg / 2 + 1));   // next group's fragment, in the MFMA shadow
-#if TG_ATT_IGLP
 #pragma unroll
                 for (int i_ = 0; i_ < CT; ++i_) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                     __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
                 }
-#endif
                 __builtin_amdgcn_sched_barrier(0);
                 if (hg & 1) xf = xfn;
             }
             TG_ASTAMP(2 + 4 * tm);
             __builtin_amdgcn_sched_barrier(0);
             // the residual rows of column tile tm, D layout (row = channel ct*16 + kq*4 + r, column = position tm*16 + j).
-            // TG_ATT_RESID_PERM (round 4, default): taken from the block's ROW registers, which hold exactly these values in the
+            // Taken from the block's ROW registers, which hold exactly these values in the
             // projection layout -- lane (j, kq') has channels g*16 + (kq' & 1)*8 .. +7 of row j, the lane pairs kq' and kq' + 2
             // hold the same eight -- so lanes kq' < 2 offer their first four, lanes kq' >= 2 their last four, and destination
             // (j, kq) pulls from (j, (kq >> 1) + 2*(kq & 1)): one ds_bpermute per register, no memory access at all.  (Round 3
             // read them from memory again: meant to be cache hits on the lines the row loads had just fetched, they were the third
             // trip to HBM -- the XCD's L2 turns over within a row block, profiles/r3_pmc_attention_x3.json: 2.19 GB fetched.)
             f32x4 xa[CT];
-#if TG_ATT_RESID_PERM
             {
                 const int src = ((((kq >> 1) + 2 * (kq & 1)) << 4) + j) << 2;          // byte address of the source lane
                 const bool hi_half = kq >= 2;
@@ -1883,14 +1838,6 @@ __global__ __launch_bounds__(256, 1) void k_attention_x3(const float* __restrict
                                    __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(s2))), __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(s3)))};
                 }
             }
-#else
-            {
-                unsigned o = tm + 1 < NT ? eoA : eoB;
-                asm volatile("" : "+v"(o));
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) xa[ct] = ld16(tile(xb, tm), o + ct * 64);
-            }
-#endif
             if (tm + 1 < NT) issue_rows(tm + 1);                                      // lands during the block's energy / output GEMMs
             __builtin_amdgcn_sched_barrier(0);                                       // (kept here: sunk to the block's end they are waited for at once)
 #pragma unroll
@@ -2118,6 +2065,7 @@ struct ProfScope {
 template <int S, int F>
 int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, float* value, float* own) {
     constexpr int P = S * S;
+    constexpr bool WIDE = F == 128 || F == 256;       // the DMA, fp16 and split chains exist at these widths only
     hipStream_t st = ctx->stream;
     const int M = rows * P;
     const int grid = (M + 127) / 128;                 // stem / head / 1x1 convs: 128 rows per workgroup
@@ -2125,224 +2073,66 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
     // still leave room for two waves per SIMD, else 2.  Measured at F=128: 128.0 -> 132.3 TFLOP/s.
     constexpr int NPT = F <= 128 ? 3 : 2;
     const int grid_f = (M + 64 * NPT - 1) / (64 * NPT);
+    // k_conv3x3_h2: (256-row tile, 128-cout part) blocks, one workgroup each -- the kernel can walk a tile list, but the hardware
+    // dispatcher balances better than a static list (512 persistent workgroups measured 0.6-2 % slower)
+    const int grid_h = (M + 255) / 256;
+    constexpr int COS = F / 128;
+    const int nblk_h2 = COS == 1 ? grid_h : (grid_h + 7) / 8 * 8 * COS;
     const double conv_flops = 2.0 * 9.0 * (double)F * (double)F * (double)M;
-    // head conv F -> 16 (6 real couts): GEMM + col2im (k_head_gemm); TG_HEAD_GEMM=0 selects the implicit-GEMM kernel it replaced
-    auto head_conv = [&](const float* in, float* outp, const float* Wg, const ConvW& cw, const float* ps, const float* pt) {
-        const char* hg = getenv("TG_HEAD_GEMM");
-        if (hg && atoi(hg) == 0) {
-            if (ps) hipLaunchKernelGGL((k_conv3x3<S, F, 16, true, 0>), dim3(grid), dim3(256), 0, st, in, outp, (const float*)nullptr, cw.w, cw.b, ps, pt, M);
-            else hipLaunchKernelGGL((k_conv3x3<S, F, 16, false, 0>), dim3(grid), dim3(256), 0, st, in, outp, (const float*)nullptr, cw.w, cw.b,
-                                    (const float*)nullptr, (const float*)nullptr, M);
-            return;
-        }
-        constexpr int TMH = 64 * (S == 9 ? 3 : 4) - 2 * (S + 1);
-        const int nt = (M + TMH - 1) / TMH, g = nt < 512 ? nt : 512;      // two workgroups per CU walk the tile list
-        if (ps) hipLaunchKernelGGL((k_head_gemm<S, F, true>), dim3(g), dim3(256), 0, st, in, outp, Wg, cw.b, ps, pt, M, nt);
-        else hipLaunchKernelGGL((k_head_gemm<S, F, false>), dim3(g), dim3(256), 0, st, in, outp, Wg, cw.b, (const float*)nullptr, (const float*)nullptr, M, nt);
+    constexpr int WQ = F / 4 + F / 4 + F;             // q|k|v projection width
+    const bool big = (long long)M * F * 4 >= (1ll << 31);
+    Chain chain = n->path.chain;
+    if (chain == CHAIN_DMA && big) chain = CHAIN_F32;
+    if (chain == CHAIN_SPLIT && big) TG_FAIL(ctx, TG_ERR_ARG, "split-precision path: rows * P * F * 4 bytes must stay below 2 GiB per activation buffer");
+    if (chain == CHAIN_F16 && (long long)M * F * 2 >= (1ll << 31)) TG_FAIL(ctx, TG_ERR_ARG, "fp16 path: rows * P * F * 2 bytes must stay below 2 GiB per activation buffer");
+    const bool h16 = chain == CHAIN_F16 || chain == CHAIN_SPLIT, x2 = chain == CHAIN_SPLIT;
+    // the fp16 chain's head conv, and the split one's with head_x2, read the conv input act16 that the last layer writes
+    const bool head16 = chain == CHAIN_F16 || (x2 && n->path.head_x2);
+    auto wsc = [&](size_t conv) { return x2 ? n->wsc + conv : nullptr; };    // split: 2^-s of conv `conv` (stem last)
+    const size_t nl = n->layers.size(), nb = n->blocks.size();
+    // next_bn(j): the BN that layer j (j == nl: the head conv) wants applied by the layer before it.  Every chain but the general f32
+    // one hands a residual block, and the fp16 / split head conv, its input relu(bn(.)) that way.
+    auto next_bn = [&](size_t j, const float** sn, const float** tn) -> bool {
+        *sn = nullptr; *tn = nullptr;
+        if (chain == CHAIN_F32) return false;
+        if (j < nl && n->layers[j].kind == 0) { const BlockW& b = n->blocks[n->layers[j].ridx]; *sn = b.s1; *tn = b.t1; return true; }
+        if (j == nl && head16) { *sn = n->s_end; *tn = n->t_end; return true; }
+        return false;
     };
-    int g0 = (int)(((size_t)M * 16 + 255) / 256); if (g0 > 65535) g0 = 65535;
-    if (n->prec == 0) {
-        if (n->in_bits) hipLaunchKernelGGL((k_bits_to_rows<S>), dim3(g0), dim3(256), 0, st, n->in_bits, n->in_slot, n->x0, rows, n->C, n->in_words);
-        else hipLaunchKernelGGL((k_obs_to_rows<S>), dim3(g0), dim3(256), 0, st, obs, n->x0, rows, n->C);
-    }
+
+    // ---- what differs between the chains: stem, residual block, attention block, head conv ----
     float* x = n->bufA; float* y = n->bufB;
-    if constexpr (F == 128 || F == 256) {
-        if (n->prec == 3) {
-            // Split-precision chain ("f32x3"): the f32 tower's arithmetic with every conv operand carried as fp16 hi + lo and all
-            // three of the four partial products on the fp16 matrix cores (k_conv3x3_h2<..., X2>): stem and tower convs; the residual stream
-            // stays f32 row-major, the dense heads are the f32 kernel, the narrow head conv runs split as well at 128 filters
-            // (k_head_gemm_x2).  Opt-in: not the default path.
-            if ((long long)M * F * 4 >= (1ll << 31)) TG_FAIL(ctx, TG_ERR_ARG, "split-precision path: rows * P * F * 4 bytes must stay below 2 GiB per activation buffer");
-            const int grid_h = (M + 255) / 256;
-            constexpr int COS = F / 128;
-            const int nblk_h2 = (COS == 1 && !TG_H2_XCD) ? grid_h : (grid_h + 7) / 8 * 8 * COS;
-            const size_t nb = n->blocks.size();
-            int g0h = (int)(((size_t)M * 8 + 255) / 256); if (g0h > 65535) g0h = 65535;
-            if (n->in_bits) hipLaunchKernelGGL((k_bits_to_rows_h<S>), dim3(g0h), dim3(256), 0, st, n->in_bits, n->in_slot, n->x0h, rows, n->C, n->in_words);
-            else hipLaunchKernelGGL((k_obs_to_rows_h<S>), dim3(g0h), dim3(256), 0, st, obs, n->x0h, rows, n->C);
-            const float* wsc = n->wsc;
-            // The layer program (attention layers allowed at 9x9): residual blocks on the split-precision convs; a Self_Attention
-            // layer reads and writes the f32 residual stream with the f32 kernels (1x1 q/k/v projection + k_attention_mfma) and,
-            // when a residual block follows, hands it relu(bn1_next(y)) already split (X2O).
-            const size_t nl = n->layers.size();
-            // the head conv on the split fp16 MFMA too (k_head_gemm_x2, F = 128): the LAST residual block then writes relu(bn_end(.))
-            // split, as it would for a block behind it, and -- when nothing else reads the f32 stream (no attention in the policy
-            // head) -- leaves the stream itself unwritten (TG_HEAD_X2=0: the f32 head conv)
-            static const bool head_x2_on = !(getenv("TG_HEAD_X2") && atoi(getenv("TG_HEAD_X2")) == 0);
-            const bool x2_head = F == 128 && head_x2_on && n->head_x2 && nl && n->layers[nl - 1].kind == 0;
-            auto next_bn = [&](size_t i, const float** sn, const float** tn) -> bool {   // layer i+1 is a residual block?
-                if (i + 1 < nl && n->layers[i + 1].kind == 0) { const BlockW& nb2 = n->blocks[n->layers[i + 1].ridx]; *sn = nb2.s1; *tn = nb2.t1; return true; }
-                if (i + 1 == nl && x2_head) { *sn = n->s_end; *tn = n->t_end; return true; }
-                *sn = nullptr; *tn = nullptr; return false;
-            };
-            constexpr int WQ = F / 4 + F / 4 + F;
-            auto attention_x2 = [&](const AttW& a, const float* xin, float* xout, const float* ps, const float* pt, _Float16* o2,
-                                    const float* sn, const float* tn) {
-                if constexpr (S == 9 && F == 128) {
-                    // one kernel per attention block: q/k/v projected inside the core, in split precision (TG_ATT_X3=0: the pair below)
-                    static const bool fused = !(getenv("TG_ATT_X3") && atoi(getenv("TG_ATT_X3")) == 0);
-                    if (fused && a.x3w) {
-                        constexpr int lds3 = (int)(sizeof(_Float16) * F / 16 * WQ * 32 + sizeof(float) * (WQ + 6 * F) + 4096);   // image, parameters, touch scratch
-                        const int nwg = (rows + 3) / 4 < 256 ? (rows + 3) / 4 : 256;
-                        if (ps) hipLaunchKernelGGL((k_attention_x3<S, F, true>), dim3(nwg), dim3(256), lds3, st, xin, xout, o2, a.x3w, a.qkv.b, a.x3sc,
-                                                   a.gamma, a.s, a.t, ps, pt, sn, tn, rows, n->range);
-                        else hipLaunchKernelGGL((k_attention_x3<S, F, false>), dim3(nwg), dim3(256), lds3, st, xin, xout, o2, a.x3w, a.qkv.b, a.x3sc,
-                                                a.gamma, a.s, a.t, ps, pt, sn, tn, rows, n->range);
-                        return;
-                    }
-                }
-                if constexpr (S == 9) {
-                    if (ps)
-                        hipLaunchKernelGGL((k_conv3x3<S, F, WQ, true, 2, 1>), dim3(grid), dim3(256), 0, st, xin, n->bufQ,
-                                           (const float*)nullptr, a.qkv.w, a.qkv.b, ps, pt, M);
-                    else
-                        hipLaunchKernelGGL((k_conv3x3<S, F, WQ, false, 2, 1>), dim3(grid), dim3(256), 0, st, xin, n->bufQ,
-                                           (const float*)nullptr, a.qkv.w, a.qkv.b, (const float*)nullptr, (const float*)nullptr, M);
-                    hipLaunchKernelGGL((k_attention_mfma<S, F, 2, true>), dim3((rows + 3) / 4), dim3(256), 0, st, (const float*)n->bufQ, xin, xout,
-                                       reinterpret_cast<float*>(o2), a.gamma, a.s, a.t, ps, pt, sn, tn, rows, n->range);
-                }
-            };
-            const float* s0 = nullptr; const float* t0 = nullptr;
-            const bool act0 = nl && n->layers[0].kind == 0;
-            if (act0) { s0 = n->blocks[n->layers[0].ridx].s1; t0 = n->blocks[n->layers[0].ridx].t1; }
-            hipLaunchKernelGGL((k_conv3x3_h2<S, 64, F, 4, false, true>), dim3(nblk_h2), dim3(256), 0, st, (const _Float16*)n->x0h, x,
-                               act0 ? n->act16 : (_Float16*)nullptr, (const float*)nullptr, (const _Float16*)n->stem_h, n->stem.b, s0, t0,
-                               M, nblk_h2, wsc + 2 * nb, n->range);
-            for (size_t i = 0; i < nl; ++i) {
-                const Layer& L = n->layers[i];
-                const float* sn; const float* tn;
-                const bool act = next_bn(i, &sn, &tn);
-                if (L.kind == 1) {
-                    attention_x2(L.a, x, y, nullptr, nullptr, act ? n->act16 : (_Float16*)nullptr, sn, tn);
-                    float* t = x; x = y; y = t;
-                    continue;
-                }
-                const BlockW& b = n->blocks[L.ridx];
-                { ProfScope ps(n, st, conv_flops);
-                  hipLaunchKernelGGL((k_conv3x3_h2<S, 2 * F, F, 0, false, true>), dim3(nblk_h2), dim3(256), 0, st, (const _Float16*)n->act16,
-                                     (float*)nullptr, n->h16, (const float*)nullptr, b.h1, b.c1.b, (const float*)nullptr, (const float*)nullptr, M, nblk_h2,
-                                     wsc + 2 * L.ridx, n->range); }
-                float* const y32 = (i + 1 == nl && x2_head && !n->pol_att) ? (float*)nullptr : y;     // nothing reads the last block's f32 stream
-                { ProfScope ps(n, st, conv_flops);
-                  hipLaunchKernelGGL((k_conv3x3_h2<S, 2 * F, F, 1, false, true>), dim3(nblk_h2), dim3(256), 0, st, (const _Float16*)n->h16,
-                                     y32, act ? n->act16 : (_Float16*)nullptr, (const float*)x, b.h2, b.c2.b, sn, tn, M, nblk_h2, wsc + 2 * L.ridx + 1, n->range); }
-                float* t = x; x = y; y = t;
+    auto stem = [&](bool act, const float* sn, const float* tn) {   // conv 16 -> F into the residual stream x
+        if constexpr (WIDE) {
+            if (h16) {   // input planes are 0/1, exact in fp16; 16 planes padded to 64 channels = 18 stages
+                auto* k = x2 ? &k_conv3x3_h2<S, 64, F, 4, false, true> : n->path.r16 ? &k_conv3x3_h2<S, 64, F, 4, true> : &k_conv3x3_h2<S, 64, F, 4>;
+                hipLaunchKernelGGL(k, dim3(nblk_h2), dim3(256), 0, st, n->x0h, x, act ? n->act16 : nullptr, nullptr, n->stem_h, n->stem.b,
+                                   sn, tn, M, nblk_h2, wsc(2 * nb), n->range);
+                return;
             }
-            if (x2_head) {
-                if constexpr (F == 128) {
-                    constexpr int TMH = 64 * (S == 9 ? 3 : 4) - 2 * (S + 1);
-                    const int nt = (M + TMH - 1) / TMH, g = nt < 512 ? nt : 512;
-                    hipLaunchKernelGGL((k_head_gemm_x2<S, F>), dim3(g), dim3(256), 0, st, (const _Float16*)n->act16, n->hc, n->head_x2, n->head_x2sc, n->head.b, M, nt);
-                }
-            } else {
-                // the head conv is 16 couts wide (one MFMA tile): the f32 kernel reads the f32 residual stream and activates while staging
-                head_conv(x, n->hc, n->head_g, n->head, n->s_end, n->t_end);
+            if (chain == CHAIN_DMA) {
+                if (n->NB) (void)hipMemsetAsync(n->tile_ctr, 0, sizeof(int) * 2 * n->NB, st);     // dynamic tile counters of the conv launches
+                hipLaunchKernelGGL((k_conv3x3<S, 16, F, false, 0, 9, 2, true>), dim3(grid), dim3(256), 0, st, n->x0, x, nullptr, n->stem.w,
+                                   n->stem.b, nullptr, nullptr, M, act ? n->bufAct : nullptr, sn, tn);
+                return;
             }
-            const float* hca3 = n->hc;
-            if (n->pol_att) {                              // attention in the policy head (model.py:72,106-107), f32 head conv behind it
-                // (the policy head conv on the split MFMA as well was measured: what it saves the attention block's extra split write
-                // of its output costs -- 723.3 vs 723.2 k sims/s -- so it reads the f32 output)
-                attention_x2(n->patt, x, y, n->s_end, n->t_end, (_Float16*)nullptr, (const float*)nullptr, (const float*)nullptr);
-                head_conv(y, n->hca, n->head_ag, n->head_a, nullptr, nullptr);
-                hca3 = n->hca;
-            }
-            hipLaunchKernelGGL((k_heads<S>), dim3((rows + HeadRows<S>::N - 1) / HeadRows<S>::N), dim3(256), 0, st, (const float*)n->hc, hca3, n->w_vo, n->b_vo,
-                               n->w_v, n->b_v, n->w_o, n->b_o, n->w_a, n->b_a, policy, value, own, rows);
-            TG_HIP(ctx, hipGetLastError());
-            return TG_OK;
         }
-        if (n->prec >= 1) {
-            // fp16 chain: every conv (stem, tower, head conv) takes fp16 operands and accumulates in f32; the small dense heads
-            // (k_heads) stay f32, and so does the residual stream x/y unless net_precision is 2 (then x/y are fp16, slice-major, and
-            // live in the same buffers; a block's output is still rounded once, from the f32 accumulator)
-            const bool r16 = n->prec == 2;
-            if ((long long)M * F * 2 >= (1ll << 31)) TG_FAIL(ctx, TG_ERR_ARG, "fp16 path: rows * P * F * 2 bytes must stay below 2 GiB per activation buffer");
-            const int grid_h = (M + 255) / 256;                                      // 256-row tiles
-            constexpr int COS = F / 128;
-            const int nblk_h2 = (COS == 1 && !TG_H2_XCD) ? grid_h : (grid_h + 7) / 8 * 8 * COS;      // (row tile, cout part) blocks
-            // one workgroup per block: the kernel can walk a tile list (grid < nblk), but the hardware dispatcher balances
-            // better than a static list -- 512 persistent workgroups measured 0.6-2 % slower
-            const int grid_h2 = nblk_h2;
-            const size_t nb = n->blocks.size();
-            // stem on the fp16 matrix cores too (input planes are 0/1, exact in fp16; 16 planes padded to 64 channels = 18 stages):
-            // writes the f32 residual stream x and the first conv input relu(bn_next(x)) as fp16
-            int g0h = (int)(((size_t)M * 8 + 255) / 256); if (g0h > 65535) g0h = 65535;
-            if (n->in_bits) hipLaunchKernelGGL((k_bits_to_rows_h<S>), dim3(g0h), dim3(256), 0, st, n->in_bits, n->in_slot, n->x0h, rows, n->C, n->in_words);
-            else hipLaunchKernelGGL((k_obs_to_rows_h<S>), dim3(g0h), dim3(256), 0, st, obs, n->x0h, rows, n->C);
-            if (r16)
-                hipLaunchKernelGGL((k_conv3x3_h2<S, 64, F, 4, true>), dim3(grid_h2), dim3(256), 0, st, (const _Float16*)n->x0h, x, n->act16,
-                                   (const float*)nullptr, (const _Float16*)n->stem_h, n->stem.b, nb ? n->blocks[0].s1 : n->s_end,
-                                   nb ? n->blocks[0].t1 : n->t_end, M, nblk_h2, (const float*)nullptr, n->range);
-            else
-                hipLaunchKernelGGL((k_conv3x3_h2<S, 64, F, 4>), dim3(grid_h2), dim3(256), 0, st, (const _Float16*)n->x0h, x, n->act16,
-                                   (const float*)nullptr, (const _Float16*)n->stem_h, n->stem.b, nb ? n->blocks[0].s1 : n->s_end,
-                                   nb ? n->blocks[0].t1 : n->t_end, M, nblk_h2, (const float*)nullptr, n->range);
-            for (size_t i = 0; i < nb; ++i) {
-                const BlockW& b = n->blocks[i];
-                const bool last = i + 1 == nb;
-                const float* sn = last ? n->s_end : n->blocks[i + 1].s1;          // the last block activates for the head conv
-                const float* tn = last ? n->t_end : n->blocks[i + 1].t1;
-                _Float16* const a16 = n->act16;
+        hipLaunchKernelGGL((k_conv3x3<S, 16, F, false, 0>), dim3(grid), dim3(256), 0, st, n->x0, x, nullptr, n->stem.w, n->stem.b, nullptr, nullptr, M);
+    };
+    auto block = [&](const BlockW& b, int ridx, float* out, bool act, const float* sn, const float* tn) {   // y = x + conv(conv(x))
+        if constexpr (WIDE) {
+            if (h16) {
+                auto* k1 = x2 ? &k_conv3x3_h2<S, 2 * F, F, 0, false, true> : &k_conv3x3_h2<S, F, F, 0>;
+                auto* k2 = x2 ? &k_conv3x3_h2<S, 2 * F, F, 1, false, true> : n->path.r16 ? &k_conv3x3_h2<S, F, F, 1, true> : &k_conv3x3_h2<S, F, F, 1>;
                 { ProfScope ps(n, st, conv_flops);
-                  hipLaunchKernelGGL((k_conv3x3_h2<S, F, F, 0>), dim3(grid_h2), dim3(256), 0, st, (const _Float16*)n->act16,
-                                     (float*)nullptr, n->h16, (const float*)nullptr, b.h1, b.c1.b, (const float*)nullptr, (const float*)nullptr, M, nblk_h2,
-                                     (const float*)nullptr, n->range); }
+                  hipLaunchKernelGGL(k1, dim3(nblk_h2), dim3(256), 0, st, n->act16, nullptr, n->h16, nullptr, b.h1, b.c1.b, nullptr, nullptr,
+                                     M, nblk_h2, wsc(2 * ridx), n->range); }
                 { ProfScope ps(n, st, conv_flops);
-                  if (r16)
-                      hipLaunchKernelGGL((k_conv3x3_h2<S, F, F, 1, true>), dim3(grid_h2), dim3(256), 0, st, (const _Float16*)n->h16,
-                                         last ? (float*)nullptr : y, a16, (const float*)x, b.h2, b.c2.b, sn, tn, M, nblk_h2, (const float*)nullptr, n->range);
-                  else
-                      hipLaunchKernelGGL((k_conv3x3_h2<S, F, F, 1>), dim3(grid_h2), dim3(256), 0, st, (const _Float16*)n->h16,
-                                         last ? (float*)nullptr : y, a16, (const float*)x, b.h2, b.c2.b, sn, tn, M, nblk_h2, (const float*)nullptr, n->range); }
-                float* t = x; x = y; y = t;
+                  hipLaunchKernelGGL(k2, dim3(nblk_h2), dim3(256), 0, st, n->h16, out, act ? n->act16 : nullptr, x, b.h2, b.c2.b, sn, tn,
+                                     M, nblk_h2, wsc(2 * ridx + 1), n->range); }
+                return;
             }
-            hipLaunchKernelGGL((k_head_h<S, F>), dim3(grid_h), dim3(256), 0, st, (const _Float16*)n->act16, n->hc,
-                               (const _Float16*)n->head_h, n->head.b, M);
-            hipLaunchKernelGGL((k_heads<S>), dim3((rows + HeadRows<S>::N - 1) / HeadRows<S>::N), dim3(256), 0, st, (const float*)n->hc, (const float*)n->hc, n->w_vo, n->b_vo,
-                               n->w_v, n->b_v, n->w_o, n->b_o, n->w_a, n->b_a, policy, value, own, rows);
-            TG_HIP(ctx, hipGetLastError());
-            return TG_OK;
-        }
-        if (n->dma && (long long)M * F * 4 < (1ll << 31)) {
-            // Prologue-free chain over the layer program: every producer (stem, the second conv of a residual block, an attention
-            // block) also writes relu(bn1_next(.)) slice-major for a residual block that follows, so the DMA-fed F->F kernels never
-            // activate anything.  Attention layers read and write the row-major residual stream (the reference's shipped
-            // MainNetwork, "RARRRARRRRAR+P", runs its nine residual blocks on k_conv3x3_sg this way).
-            const size_t nl = n->layers.size();
-            auto next_bn = [&](size_t i, const float** sn, const float** tn) -> bool {   // layer i+1 is a residual block?
-                if (i + 1 < nl && n->layers[i + 1].kind == 0) { const BlockW& nb2 = n->blocks[n->layers[i + 1].ridx]; *sn = nb2.s1; *tn = nb2.t1; return true; }
-                *sn = nullptr; *tn = nullptr; return false;
-            };
-            const float* s0 = nullptr; const float* t0 = nullptr;
-            const bool act0 = nl && n->layers[0].kind == 0;
-            if (act0) { s0 = n->blocks[n->layers[0].ridx].s1; t0 = n->blocks[n->layers[0].ridx].t1; }
-            if (n->NB) (void)hipMemsetAsync(n->tile_ctr, 0, sizeof(int) * 2 * n->NB, st);     // dynamic tile counters of the conv launches
-            hipLaunchKernelGGL((k_conv3x3<S, 16, F, false, 0, 9, 2, true>), dim3(grid), dim3(256), 0, st, (const float*)n->x0, x,
-                               (const float*)nullptr, n->stem.w, n->stem.b, (const float*)nullptr, (const float*)nullptr, M,
-                               act0 ? n->bufAct : (float*)nullptr, s0, t0);
-            constexpr int WQ = F / 4 + F / 4 + F;
-            auto attention_fast = [&](const AttW& a, const float* xin, float* xout, const float* ps, const float* pt, float* o2,
-                                      const float* sn, const float* tn) {
-                if (ps)
-                    hipLaunchKernelGGL((k_conv3x3<S, F, WQ, true, 2, 1>), dim3(grid), dim3(256), 0, st, xin, n->bufQ,
-                                       (const float*)nullptr, a.qkv.w, a.qkv.b, ps, pt, M);
-                else
-                    hipLaunchKernelGGL((k_conv3x3<S, F, WQ, false, 2, 1>), dim3(grid), dim3(256), 0, st, xin, n->bufQ,
-                                       (const float*)nullptr, a.qkv.w, a.qkv.b, (const float*)nullptr, (const float*)nullptr, M);
-                if constexpr (S == 9)
-                    hipLaunchKernelGGL((k_attention_mfma<S, F, 2>), dim3((rows + 3) / 4), dim3(256), 0, st, (const float*)n->bufQ, xin, xout,
-                                       o2, a.gamma, a.s, a.t, ps, pt, sn, tn, rows);
-            };
-            for (size_t i = 0; i < nl; ++i) {
-                const Layer& L = n->layers[i];
-                const float* sn; const float* tn;
-                const bool act = next_bn(i, &sn, &tn);
-                if (L.kind == 1) {
-                    attention_fast(L.a, x, y, nullptr, nullptr, act ? n->bufAct : (float*)nullptr, sn, tn);
-                    float* t = x; x = y; y = t;
-                    continue;
-                }
-                const BlockW& b = n->blocks[L.ridx];
+            if (chain == CHAIN_DMA) {
                 // tile shape per launch (F = 128): rows one full round of resident workgroups covers = 768 x 192 or 1024 x 128; take the
                 // shape whose rounded-up round count wastes fewer rows (ties: the larger tile)
                 bool small_tiles = false;
@@ -2353,83 +2143,116 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
                 const int SD_TM = F == 128 ? (small_tiles ? 128 : 192) : 128;
                 const int ntile_sd = (M + SD_TM - 1) / SD_TM, slots_sd = F == 128 ? ntile_sd : 512;  // F=256: 2 resident workgroups x 256 CUs walk a dynamic tile list
                 int grid_sd = ntile_sd < slots_sd ? ntile_sd : slots_sd;
-                if (TG_SG_XCD && F == 128) grid_sd = (grid_sd + 7) / 8 * 8;
-                int* const ctr1 = n->tile_ctr + 2 * L.ridx; int* const ctr2 = ctr1 + 1;              // zeroed at the top of the forward
-                float* const actn = act ? n->bufAct : (float*)nullptr;
+                if (F == 128) grid_sd = (grid_sd + 7) / 8 * 8;                                      // XCD-contiguous tile order
+                int* const ctr = n->tile_ctr + 2 * ridx;                                            // zeroed by the stem
+                auto* k1 = small_tiles ? &k_conv3x3_sg<S, F, 0, 2> : &k_conv3x3_sg<S, F, 0>;
+                auto* k2 = small_tiles ? &k_conv3x3_sg<S, F, 1, 2> : &k_conv3x3_sg<S, F, 1>;
                 { ProfScope ps(n, st, conv_flops);
-                  if (small_tiles)
-                      hipLaunchKernelGGL((k_conv3x3_sg<S, F, 0, 2>), dim3(grid_sd), dim3(256), 0, st, (const float*)n->bufAct, n->bufH,
-                                         (const float*)nullptr, b.g1, b.c1.b, (float*)nullptr, (const float*)nullptr, (const float*)nullptr, M, ctr1);
-                  else
-                      hipLaunchKernelGGL((k_conv3x3_sg<S, F, 0>), dim3(grid_sd), dim3(256), 0, st, (const float*)n->bufAct, n->bufH,
-                                         (const float*)nullptr, b.g1, b.c1.b, (float*)nullptr, (const float*)nullptr, (const float*)nullptr, M, ctr1); }
+                  hipLaunchKernelGGL(k1, dim3(grid_sd), dim3(256), 0, st, n->bufAct, n->bufH, nullptr, b.g1, b.c1.b, nullptr, nullptr, nullptr, M, ctr); }
                 { ProfScope ps(n, st, conv_flops);
-                  if (small_tiles)
-                      hipLaunchKernelGGL((k_conv3x3_sg<S, F, 1, 2>), dim3(grid_sd), dim3(256), 0, st, (const float*)n->bufH, y,
-                                         (const float*)x, b.g2, b.c2.b, actn, sn, tn, M, ctr2);
-                  else
-                      hipLaunchKernelGGL((k_conv3x3_sg<S, F, 1>), dim3(grid_sd), dim3(256), 0, st, (const float*)n->bufH, y,
-                                         (const float*)x, b.g2, b.c2.b, actn, sn, tn, M, ctr2); }
-                float* t = x; x = y; y = t;
+                  hipLaunchKernelGGL(k2, dim3(grid_sd), dim3(256), 0, st, n->bufH, out, x, b.g2, b.c2.b, act ? n->bufAct : nullptr, sn, tn, M, ctr + 1); }
+                return;
             }
-            // bufAct / bufH are slice-major; the head convs read the row-major residual stream and activate it while staging
-            head_conv(x, n->hc, n->head_g, n->head, n->s_end, n->t_end);
-            const float* hca = n->hc;
-            if (n->pol_att) {                              // attention in the policy head (model.py:72,106-107) on relu(bn_end(x))
-                attention_fast(n->patt, x, y, n->s_end, n->t_end, (float*)nullptr, (const float*)nullptr, (const float*)nullptr);
-                head_conv(y, n->hca, n->head_ag, n->head_a, nullptr, nullptr);
-                hca = n->hca;
-            }
-            hipLaunchKernelGGL((k_heads<S>), dim3((rows + HeadRows<S>::N - 1) / HeadRows<S>::N), dim3(256), 0, st, (const float*)n->hc, hca, n->w_vo, n->b_vo,
-                               n->w_v, n->b_v, n->w_o, n->b_o, n->w_a, n->b_a, policy, value, own, rows);
-            TG_HIP(ctx, hipGetLastError());
-            return TG_OK;
         }
-    }
-    hipLaunchKernelGGL((k_conv3x3<S, 16, F, false, 0>), dim3(grid), dim3(256), 0, st, (const float*)n->x0, x,
-                       (const float*)nullptr, n->stem.w, n->stem.b, (const float*)nullptr, (const float*)nullptr, M);
-    // attention block: fused q|k|v 1x1 projection on the matrix cores, then the per-board core (model.py:301-315)
-    constexpr int W = F / 4 + F / 4 + F;
-    constexpr size_t att_lds = sizeof(float) * ((size_t)P * W + (size_t)P * (P + 1));
-    auto attention = [&](const AttW& a, const float* xin, float* xout, const float* ps, const float* pt) -> int {
-        if (att_lds > 160 * 1024) return -1;
-        if (ps)
-            hipLaunchKernelGGL((k_conv3x3<S, F, W, true, 2, 1>), dim3(grid), dim3(256), 0, st, xin, n->bufQ,
-                               (const float*)nullptr, a.qkv.w, a.qkv.b, ps, pt, M);
-        else
-            hipLaunchKernelGGL((k_conv3x3<S, F, W, false, 2, 1>), dim3(grid), dim3(256), 0, st, xin, n->bufQ,
-                               (const float*)nullptr, a.qkv.w, a.qkv.b, (const float*)nullptr, (const float*)nullptr, M);
-        hipLaunchKernelGGL((k_attention<S, F>), dim3(rows), dim3(256), att_lds, st, (const float*)n->bufQ, xin, xout,
-                           a.gamma, a.s, a.t, ps, pt);
+        { ProfScope ps(n, st, conv_flops);
+          hipLaunchKernelGGL((k_conv3x3<S, F, F, true, 0, 9, NPT>), dim3(grid_f), dim3(256), 0, st, x, n->bufH, nullptr, b.c1.w, b.c1.b, b.s1, b.t1, M); }
+        { ProfScope ps(n, st, conv_flops);
+          hipLaunchKernelGGL((k_conv3x3<S, F, F, false, 1, 9, NPT>), dim3(grid_f), dim3(256), 0, st, n->bufH, out, x, b.c2.w, b.c2.b, nullptr, nullptr, M); }
+    };
+    // Self_Attention block (model.py:301-315) xin -> xout; ps/pt: the policy head's relu(bn_end(.)) first.  Non-zero: no kernel fits.
+    auto attention = [&](const AttW& a, const float* xin, float* xout, const float* ps, const float* pt, bool act, const float* sn, const float* tn) -> int {
+        if constexpr (S == 9 && F == 128) {
+            if (x2) {   // one kernel per block: q/k/v projected inside the core, in split precision
+                constexpr int lds3 = (int)(sizeof(_Float16) * F / 16 * WQ * 32 + sizeof(float) * (WQ + 6 * F) + 4096);   // image, parameters, touch scratch
+                const int nwg = (rows + 3) / 4 < 256 ? (rows + 3) / 4 : 256;
+                auto* k = ps ? &k_attention_x3<S, F, true> : &k_attention_x3<S, F, false>;
+                hipLaunchKernelGGL(k, dim3(nwg), dim3(256), lds3, st, xin, xout, act ? n->act16 : nullptr, a.x3w, a.qkv.b, a.x3sc,
+                                   a.gamma, a.s, a.t, ps, pt, sn, tn, rows, n->range);
+                return 0;
+            }
+        }
+        if (chain == CHAIN_F32 && !n->path.att_lds) return -1;
+        // the fused q|k|v 1x1 projection on the matrix cores, then the per-board core
+        auto* kq = ps ? &k_conv3x3<S, F, WQ, true, 2, 1> : &k_conv3x3<S, F, WQ, false, 2, 1>;
+        hipLaunchKernelGGL(kq, dim3(grid), dim3(256), 0, st, xin, n->bufQ, nullptr, a.qkv.w, a.qkv.b, ps, pt, M, nullptr, nullptr, nullptr);
+        // the MFMA core, one wave per board, writes the next residual block's input too (split: as hi + lo)
+        if constexpr (S == 9 && F == 256) {
+            if (x2) {
+                hipLaunchKernelGGL((k_attention_mfma<S, F, 2, true>), dim3((rows + 3) / 4), dim3(256), 0, st, n->bufQ, xin, xout,
+                                   reinterpret_cast<float*>(act ? n->act16 : nullptr), a.gamma, a.s, a.t, ps, pt, sn, tn, rows, n->range);
+                return 0;
+            }
+        }
+        if constexpr (S == 9 && WIDE) {
+            if (chain == CHAIN_DMA) {
+                hipLaunchKernelGGL((k_attention_mfma<S, F, 2>), dim3((rows + 3) / 4), dim3(256), 0, st, n->bufQ, xin, xout,
+                                   act ? n->bufAct : nullptr, a.gamma, a.s, a.t, ps, pt, sn, tn, rows);
+                return 0;
+            }
+        }
+        hipLaunchKernelGGL((k_attention<S, F>), dim3(rows), dim3(256), n->path.att_lds, st, n->bufQ, xin, xout, a.gamma, a.s, a.t, ps, pt);
         return 0;
     };
-    for (const Layer& L : n->layers) {
+    // head conv F -> 16 (6 real couts) on relu(bn(in)) (ps/pt) or on in: GEMM + col2im (k_head_gemm); TG_HEAD_GEMM=0 selects the
+    // implicit-GEMM kernel it replaced
+    auto head_conv = [&](const float* in, float* outp, const float* Wg, const ConvW& cw, const float* ps, const float* pt) {
+        const char* hg = getenv("TG_HEAD_GEMM");
+        if (hg && atoi(hg) == 0) {
+            auto* k = ps ? &k_conv3x3<S, F, 16, true, 0> : &k_conv3x3<S, F, 16, false, 0>;
+            hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, in, outp, nullptr, cw.w, cw.b, ps, pt, M, nullptr, nullptr, nullptr);
+            return;
+        }
+        constexpr int TMH = 64 * (S == 9 ? 3 : 4) - 2 * (S + 1);
+        const int nt = (M + TMH - 1) / TMH, g = nt < 512 ? nt : 512;      // two workgroups per CU walk the tile list
+        auto* k = ps ? &k_head_gemm<S, F, true> : &k_head_gemm<S, F, false>;
+        hipLaunchKernelGGL(k, dim3(g), dim3(256), 0, st, in, outp, Wg, cw.b, ps, pt, M, nt);
+    };
+
+    // ---- the forward: input planes, stem, layers, head convs, dense heads ----
+    if (h16) {
+        int g0h = (int)(((size_t)M * 8 + 255) / 256); if (g0h > 65535) g0h = 65535;
+        if (n->in_bits) hipLaunchKernelGGL((k_bits_to_rows_h<S>), dim3(g0h), dim3(256), 0, st, n->in_bits, n->in_slot, n->x0h, rows, n->C, n->in_words);
+        else hipLaunchKernelGGL((k_obs_to_rows_h<S>), dim3(g0h), dim3(256), 0, st, obs, n->x0h, rows, n->C);
+    } else {
+        int g0 = (int)(((size_t)M * 16 + 255) / 256); if (g0 > 65535) g0 = 65535;
+        if (n->in_bits) hipLaunchKernelGGL((k_bits_to_rows<S>), dim3(g0), dim3(256), 0, st, n->in_bits, n->in_slot, n->x0, rows, n->C, n->in_words);
+        else hipLaunchKernelGGL((k_obs_to_rows<S>), dim3(g0), dim3(256), 0, st, obs, n->x0, rows, n->C);
+    }
+    const float* sn; const float* tn;
+    { const bool act = next_bn(0, &sn, &tn); stem(act, sn, tn); }
+    for (size_t i = 0; i < nl; ++i) {
+        const Layer& L = n->layers[i];
+        const bool act = next_bn(i + 1, &sn, &tn);
         if (L.kind == 1) {
-            if (attention(L.a, x, y, nullptr, nullptr)) TG_FAIL(ctx, TG_ERR_ARG, "attention blocks need P*(1.5F+P+1) floats of LDS: not available at this board size");
-            float* t = x; x = y; y = t;
-            continue;
-        }
-        const BlockW& b = n->blocks[L.ridx];
-        { ProfScope ps(n, st, conv_flops);
-          hipLaunchKernelGGL((k_conv3x3<S, F, F, true, 0, 9, NPT>), dim3(grid_f), dim3(256), 0, st, (const float*)x, n->bufH,
-                             (const float*)nullptr, b.c1.w, b.c1.b, b.s1, b.t1, M);
-        }
-        { ProfScope ps(n, st, conv_flops);
-          hipLaunchKernelGGL((k_conv3x3<S, F, F, false, 1, 9, NPT>), dim3(grid_f), dim3(256), 0, st, (const float*)n->bufH, y,
-                             (const float*)x, b.c2.w, b.c2.b, (const float*)nullptr, (const float*)nullptr, M);
+            if (attention(L.a, x, y, nullptr, nullptr, act, sn, tn)) TG_FAIL(ctx, TG_ERR_ARG, "attention blocks need P*(1.5F+P+1) floats of LDS: not available at this board size");
+        } else {
+            // nothing reads the last block's f32 stream when the head conv takes act16 and no policy attention follows
+            block(n->blocks[L.ridx], L.ridx, i + 1 == nl && head16 && !n->pol_att ? nullptr : y, act, sn, tn);
         }
         float* t = x; x = y; y = t;
     }
     // heads: value/ownership conv reads relu(bn_end(x)) (model.py:94,97); the policy conv reads the same tensor, or its
     // Self_Attention when the architecture has attention_act (model.py:72,106-107)
-    head_conv(x, n->hc, n->head_g, n->head, n->s_end, n->t_end);
+    if (!head16) {
+        head_conv(x, n->hc, n->head_g, n->head, n->s_end, n->t_end);
+    } else if constexpr (WIDE) {
+        if (!x2) {
+            hipLaunchKernelGGL((k_head_h<S, F>), dim3(grid_h), dim3(256), 0, st, n->act16, n->hc, n->head_h, n->head.b, M);
+        } else if constexpr (F == 128) {
+            constexpr int TMH = 64 * (S == 9 ? 3 : 4) - 2 * (S + 1);
+            const int nt = (M + TMH - 1) / TMH, g = nt < 512 ? nt : 512;
+            hipLaunchKernelGGL((k_head_gemm_x2<S, F>), dim3(g), dim3(256), 0, st, n->act16, n->hc, n->head_x2, n->head_x2sc, n->head.b, M, nt);
+        }
+    }
     const float* hca = n->hc;
     if (n->pol_att) {
-        if (attention(n->patt, x, y, n->s_end, n->t_end)) TG_FAIL(ctx, TG_ERR_ARG, "attention policy head: not enough LDS at this board size");
+        // the f32 head conv reads the attention's f32 output in the split chain too (the policy head conv on the split MFMA was
+        // measured: what it saves the attention block's extra split write of its output costs -- 723.3 vs 723.2 k sims/s)
+        if (attention(n->patt, x, y, n->s_end, n->t_end, false, nullptr, nullptr)) TG_FAIL(ctx, TG_ERR_ARG, "attention policy head: not enough LDS at this board size");
         head_conv(y, n->hca, n->head_ag, n->head_a, nullptr, nullptr);
         hca = n->hca;
     }
-    hipLaunchKernelGGL((k_heads<S>), dim3((rows + HeadRows<S>::N - 1) / HeadRows<S>::N), dim3(256), 0, st, (const float*)n->hc, hca, n->w_vo, n->b_vo, n->w_v, n->b_v,
+    hipLaunchKernelGGL((k_heads<S>), dim3((rows + HeadRows<S>::N - 1) / HeadRows<S>::N), dim3(256), 0, st, n->hc, hca, n->w_vo, n->b_vo, n->w_v, n->b_v,
                        n->w_o, n->b_o, n->w_a, n->b_a, policy, value, own, rows);
     TG_HIP(ctx, hipGetLastError());
     return TG_OK;
@@ -2505,7 +2328,7 @@ void bind_weights(Net* n, int k) {
             b.c1.w = take(per); b.c1.b = take(F);
             b.c2.w = take(per); b.c2.b = take(F);
             b.g1 = w.wstage ? w.wstage + (size_t)(2 * ri) * per : nullptr; b.g2 = w.wstage ? w.wstage + (size_t)(2 * ri + 1) * per : nullptr;
-            const size_t perh = n->prec == 3 ? 2 * per : per;           // split precision: hi + lo halves of every weight
+            const size_t perh = n->path.chain == CHAIN_SPLIT ? 2 * per : per;   // split precision: hi + lo halves of every weight
             b.h1 = w.wh ? w.wh + (size_t)(2 * ri) * perh : nullptr; b.h2 = w.wh ? w.wh + (size_t)(2 * ri + 1) * perh : nullptr;
             L.ridx = ri++;
         } else {
@@ -2537,7 +2360,8 @@ int fill_weight_set(tg_ctx* ctx, Net* n, int k, const float* blob, hipStream_t s
     bind_weights(&view, k);
     hipLaunchKernelGGL(k_restage_head, dim3(64), dim3(256), 0, st, view.head.w, n->sets[k].head_g, F);
     if (n->pol_att) hipLaunchKernelGGL(k_restage_head, dim3(64), dim3(256), 0, st, view.head_a.w, n->sets[k].head_ag, F);
-    if (n->prec == 3) {
+    const NetPath& p = n->path;
+    if (p.chain == CHAIN_SPLIT) {
         // split copies (hi | lo of w * 2^s per conv), made on the device from the blob just uploaded; the scale words double as the
         // scratch of the abs-max reduction (bit patterns), overwritten with 2^-s by the restaging kernel that follows in order
         const size_t nconv = 2 * view.blocks.size() + 1;
@@ -2553,7 +2377,7 @@ int fill_weight_set(tg_ctx* ctx, Net* n, int k, const float* blob, hipStream_t s
                 ++ci;
             }
         }
-        if (n->sets[k].att_h) {                                                       // fused attention layers: split q|k|v weights
+        if (p.att_x3) {                                                               // fused attention layers: split q|k|v weights
             std::vector<const AttW*> atts;
             for (const Layer& L : view.layers) if (L.kind == 1) atts.push_back(&L.a);
             if (n->pol_att) atts.push_back(&view.patt);
@@ -2569,14 +2393,14 @@ int fill_weight_set(tg_ctx* ctx, Net* n, int k, const float* blob, hipStream_t s
         hipLaunchKernelGGL(k_absmax, dim3(64), dim3(256), 0, st, view.stem.w, (size_t)9 * F * 16, mx + ci);
         hipLaunchKernelGGL(k_restage_split, dim3(256), dim3(256), 0, st, view.stem.w, view.stem_h, n->sets[k].wsc + ci, (const unsigned*)(mx + ci),
                            F, 16, 2, 1);                                              // 16 planes = one group, padded to two (an even stage count)
-        if (n->sets[k].head_x2) {
+        if (p.head_x2) {
             unsigned* hmx = reinterpret_cast<unsigned*>(n->sets[k].head_x2sc) + 1;
             TG_HIP(ctx, hipMemsetAsync(hmx, 0, sizeof(unsigned), st));
             hipLaunchKernelGGL(k_absmax, dim3(16), dim3(256), 0, st, view.head.w, (size_t)9 * 16 * F, hmx);
             hipLaunchKernelGGL(k_restage_head_split, dim3(32), dim3(256), 0, st, view.head.w, n->sets[k].head_x2, n->sets[k].head_x2sc, (const unsigned*)hmx, F);
         }
         TG_HIP(ctx, hipGetLastError());
-    } else if (n->prec >= 1) {
+    } else if (p.chain == CHAIN_F16) {
         // stage-ordered fp16 copies, converted on the device from the blob just uploaded (round to nearest even)
         for (const BlockW& b : view.blocks) {
             hipLaunchKernelGGL(k_restage_half, dim3(1024), dim3(256), 0, st, b.c1.w, const_cast<_Float16*>(b.h1), F, F, F, 32, 1);   // k_conv3x3_h2: 32-channel stages, paired couts
@@ -2585,7 +2409,7 @@ int fill_weight_set(tg_ctx* ctx, Net* n, int k, const float* blob, hipStream_t s
         hipLaunchKernelGGL(k_restage_half, dim3(256), dim3(256), 0, st, view.stem.w, view.stem_h, F, 16, 64, 32, 1);
         hipLaunchKernelGGL(k_restage_half, dim3(256), dim3(256), 0, st, view.head.w, view.head_h, 16, F, F, 32, 0);
         TG_HIP(ctx, hipGetLastError());
-    } else if (n->dma) {
+    } else if (p.chain == CHAIN_DMA) {
         // stage-ordered copy for k_conv3x3_sg, [slice*9 + tap][cout][16 channels of the slice], made on the device
         for (const BlockW& b : view.blocks) {
             hipLaunchKernelGGL(k_restage_f32, dim3(1024), dim3(256), 0, st, b.c1.w, const_cast<float*>(b.g1), F);
@@ -2608,6 +2432,25 @@ int adopt_pending(tg_ctx* ctx, Net* n, bool wait) {
     n->pending = false;
     TG_HIP(ctx, hipEventRecord(n->swapped, ctx->stream));               // kernels already queued may still read the retired set
     return TG_OK;
+}
+
+// The forward's path for a network of this shape and precision (tg_net_load_arch has rejected the unsupported combinations).
+NetPath net_path(int S, int F, int prec, const std::string& trunk, bool pol) {
+    const size_t P = (size_t)S * S, Wq = (size_t)F / 4 * 2 + F;
+    const bool any_att = pol || trunk.find('A') != std::string::npos;
+    NetPath p;
+    if (prec == 3) p.chain = CHAIN_SPLIT;
+    else if (prec >= 1) p.chain = CHAIN_F16;
+    else if ((F == 128 || F == 256) && (!any_att || S == 9)) {          // attention layers need the 9x9 MFMA kernel
+        const char* dma = getenv("TG_DMA_CONV");
+        p.chain = dma && atoi(dma) == 0 ? CHAIN_F32 : CHAIN_DMA;
+    }
+    p.r16 = prec == 2;
+    p.att_x3 = prec == 3 && any_att && F == 128 && S == 9;
+    p.head_x2 = prec == 3 && F == 128 && !trunk.empty() && trunk.back() == 'R';
+    const size_t lds = sizeof(float) * (P * Wq + P * (P + 1));
+    p.att_lds = any_att && lds <= 160 * 1024 ? lds : 0;
+    return p;
 }
 
 }  // namespace
@@ -2656,6 +2499,8 @@ int tg_net_load_arch(tg_ctx* ctx, const char* arch_c, const float* blob, size_t 
         e->net = n;
         n->S = S; n->P = (int)P; n->A = (int)A; n->C = C; n->F = F; n->NB = NB; n->rows_cap = rows_cap; n->arch = arch; n->pol_att = pol;
         n->blob_floats = n_floats; n->prec = prec;
+        const NetPath& p = n->path = net_path(S, F, prec, trunk, pol);
+        const bool h16 = p.chain == CHAIN_F16 || p.chain == CHAIN_SPLIT, x2 = p.chain == CHAIN_SPLIT;
         const size_t act = sizeof(float) * (size_t)rows_cap * P * F;
         TG_HIP(ctx, hipMalloc((void**)&n->bufA, act));
         TG_HIP(ctx, hipMalloc((void**)&n->bufB, act));
@@ -2668,36 +2513,33 @@ int tg_net_load_arch(tg_ctx* ctx, const char* arch_c, const float* blob, size_t 
 
         if (any_att) TG_HIP(ctx, hipMalloc((void**)&n->bufQ, sizeof(float) * (size_t)rows_cap * P * Wq));
         if (pol) TG_HIP(ctx, hipMalloc((void**)&n->hca, sizeof(float) * (size_t)rows_cap * P * 16));
-        // DMA-fed F->F chain: f32 towers of 128 / 256 filters, with or without attention layers (those need the 9x9 MFMA kernel)
-        n->dma = ((F == 128 || F == 256) && (!any_att || S == 9)) ? (getenv("TG_DMA_CONV") ? (atoi(getenv("TG_DMA_CONV")) != 0) : 1) : 0;
-        if (prec >= 1) n->dma = 0;
         const size_t wcopy = (size_t)(NB > 0 ? 2 * NB : 1) * 9 * F * F;
-        if (n->dma) TG_HIP(ctx, hipMalloc((void**)&n->bufAct, act));
-        if (n->dma) TG_HIP(ctx, hipMalloc((void**)&n->tile_ctr, sizeof(int) * (size_t)(NB > 0 ? 2 * NB : 1)));
+        if (p.chain == CHAIN_DMA) TG_HIP(ctx, hipMalloc((void**)&n->bufAct, act));
+        if (p.chain == CHAIN_DMA) TG_HIP(ctx, hipMalloc((void**)&n->tile_ctr, sizeof(int) * (size_t)(NB > 0 ? 2 * NB : 1)));
         for (Net::WeightSet& w : n->sets) {
             TG_HIP(ctx, hipMalloc((void**)&w.blob, sizeof(float) * n_floats));
             TG_HIP(ctx, hipMalloc((void**)&w.head_g, sizeof(float) * 64 * (size_t)F));
             if (pol) TG_HIP(ctx, hipMalloc((void**)&w.head_ag, sizeof(float) * 64 * (size_t)F));
-            if (n->dma) TG_HIP(ctx, hipMalloc((void**)&w.wstage, sizeof(float) * wcopy));
-            if (prec >= 1) {
-                TG_HIP(ctx, hipMalloc((void**)&w.wh, sizeof(_Float16) * wcopy * (prec == 3 ? 2 : 1)));
-                if (prec == 3) TG_HIP(ctx, hipMalloc((void**)&w.wsc, sizeof(float) * 2 * (size_t)(2 * NB + 1)));
-                if (prec == 3 && F == 128) {                                         // split-precision head conv (k_head_gemm_x2)
-                    TG_HIP(ctx, hipMalloc((void**)&w.head_x2, sizeof(_Float16) * 64 * (size_t)F * 2));
-                    TG_HIP(ctx, hipMalloc((void**)&w.head_x2sc, sizeof(float) * 2));
-                }
-                if (prec == 3 && any_att && F == 128 && S == 9) {                    // k_attention_x3 (its weight image must fit LDS)
-                    size_t n_att = pol ? 1 : 0; for (char c : trunk) n_att += c == 'A';
-                    TG_HIP(ctx, hipMalloc((void**)&w.att_h, sizeof(_Float16) * n_att * ((size_t)F / 16 * Wq * 32)));
-                    TG_HIP(ctx, hipMalloc((void**)&w.att_sc, sizeof(float) * 2 * n_att));
-                }
+            if (p.chain == CHAIN_DMA) TG_HIP(ctx, hipMalloc((void**)&w.wstage, sizeof(float) * wcopy));
+            if (h16) {
+                TG_HIP(ctx, hipMalloc((void**)&w.wh, sizeof(_Float16) * wcopy * (x2 ? 2 : 1)));
                 TG_HIP(ctx, hipMalloc((void**)&w.stem_h, sizeof(_Float16) * 9 * (size_t)F * 64));
-                TG_HIP(ctx, hipMalloc((void**)&w.head_h, sizeof(_Float16) * 9 * 16 * (size_t)F));
+            }
+            if (p.chain == CHAIN_F16) TG_HIP(ctx, hipMalloc((void**)&w.head_h, sizeof(_Float16) * 9 * 16 * (size_t)F));
+            if (x2) TG_HIP(ctx, hipMalloc((void**)&w.wsc, sizeof(float) * 2 * (size_t)(2 * NB + 1)));
+            if (p.head_x2) {
+                TG_HIP(ctx, hipMalloc((void**)&w.head_x2, sizeof(_Float16) * 64 * (size_t)F * 2));
+                TG_HIP(ctx, hipMalloc((void**)&w.head_x2sc, sizeof(float) * 2));
+            }
+            if (p.att_x3) {                                                      // its weight image must fit LDS
+                size_t n_att = pol ? 1 : 0; for (char c : trunk) n_att += c == 'A';
+                TG_HIP(ctx, hipMalloc((void**)&w.att_h, sizeof(_Float16) * n_att * ((size_t)F / 16 * Wq * 32)));
+                TG_HIP(ctx, hipMalloc((void**)&w.att_sc, sizeof(float) * 2 * n_att));
             }
         }
-        if (prec >= 1) {
-            TG_HIP(ctx, hipMalloc((void**)&n->act16, prec == 3 ? act : act / 2));     // split precision: hi + lo per element
-            TG_HIP(ctx, hipMalloc((void**)&n->h16, prec == 3 ? act : act / 2));
+        if (h16) {
+            TG_HIP(ctx, hipMalloc((void**)&n->act16, x2 ? act : act / 2));     // split precision: hi + lo per element
+            TG_HIP(ctx, hipMalloc((void**)&n->h16, x2 ? act : act / 2));
             TG_HIP(ctx, hipMalloc((void**)&n->x0h, sizeof(_Float16) * (size_t)rows_cap * P * 64));
         }
         TG_HIP(ctx, hipStreamCreateWithFlags(&n->side, hipStreamNonBlocking));
@@ -2706,20 +2548,17 @@ int tg_net_load_arch(tg_ctx* ctx, const char* arch_c, const float* blob, size_t 
         TG_HIP(ctx, hipEventRecord(n->swapped, ctx->stream));
         TG_HIP(ctx, hipHostMalloc((void**)&n->pinned, sizeof(float) * n_floats, hipHostMallocDefault));
         n->active = 1;                                    // the load below fills set 0 and makes it the live one
-        if (prec == 3 && any_att && F == 128 && S == 9) {
+        if (p.att_x3) {
             const int lds3 = (int)(sizeof(_Float16) * (size_t)F / 16 * Wq * 32 + sizeof(float) * (Wq + 6 * (size_t)F) + 4096);
             TG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention_x3<9, 128, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds3));
             TG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention_x3<9, 128, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds3));
         }
-        if (any_att) {
-            const size_t lds = sizeof(float) * (P * Wq + P * (P + 1));
-            if (lds <= 160 * 1024) {
-                hipError_t er = hipSuccess;
-#define TG_ATT_ATTR(SZ, FF) if (S == SZ && F == FF) er = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention<SZ, FF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                TG_ATT_ATTR(9, 32); TG_ATT_ATTR(9, 64); TG_ATT_ATTR(9, 128); TG_ATT_ATTR(9, 256);
+        if (p.att_lds) {
+            hipError_t er = hipSuccess;
+#define TG_ATT_ATTR(SZ, FF) if (S == SZ && F == FF) er = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention<SZ, FF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.att_lds)
+            TG_ATT_ATTR(9, 32); TG_ATT_ATTR(9, 64); TG_ATT_ATTR(9, 128); TG_ATT_ATTR(9, 256);
 #undef TG_ATT_ATTR
-                TG_HIP(ctx, er);
-            }
+            TG_HIP(ctx, er);
         }
     }
     // Synchronous refresh (trainer.py:76-79 -> self_play.py:913): an asynchronous one still in flight is adopted first, then the
