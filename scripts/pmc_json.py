@@ -41,15 +41,15 @@ for k in sorted(set(fe) | set(wr)):
     e = {"launches_summarised": len(f), "grid_size_median": grid, "FETCH_SIZE_KB_raw_median": round(fk, 1), "WRITE_SIZE_KB_median": round(wk, 1),
          "hbm_bytes_per_launch": round((2 * fk + wk) * 1024.0, 1), "duration_us_median": round(statistics.median(x[2] for x in f) / 1e3, 2)}
     if conv:
-        npt, epi = int(k.split(",")[3].strip(" >")), int(k.split(",")[2])                     # k_conv3x3_sg<S, F, EPI, NPT>
-        rows = grid / 256 * 64 * npt
+        epi = int(k.split(",")[2].strip(" >"))                                                # k_conv3x3_sg<S, F, EPI>
+        rows = grid / 256 * 128                        # one workgroup per (128 boards, position): workgroups * 128 = boards * P = rows
         alg = (8 * F if epi == 0 else 16 * F) * rows
-        e.update(tile_rows=64 * npt, rows_per_launch_approx=int(rows), algorithmic_bytes_per_launch=int(alg),
+        e.update(boards_per_workgroup=128, rows_per_launch_approx=int(rows), algorithmic_bytes_per_launch=int(alg),
                  traffic_over_algorithmic=round(e["hbm_bytes_per_launch"] / alg, 3))
     out["kernels"][k] = e
 convs = [v for k, v in out["kernels"].items() if "k_conv3x3_sg" in k and v["launches_summarised"] > 50]
-out["dominant_kernel"] = ("k_conv3x3_sg<9,128,EPI,NPT> (EPI 0: relu; EPI 1: residual + next block's activated input; NPT 3 / 2: 192- / 128-row "
-                          "tiles, chosen per launch)")
+out["dominant_kernel"] = ("k_conv3x3_sg<9,128,EPI> (EPI 0: relu; EPI 1: residual + next block's activated input; one workgroup per board "
+                          "position x 128 boards, off-board taps skipped)")
 out["hbm_bytes_per_launch_mean"] = sum(v["hbm_bytes_per_launch"] for v in convs) / len(convs)
 out["algorithmic_bytes_per_launch_mean"] = sum(v["algorithmic_bytes_per_launch"] for v in convs) / len(convs)
 tc, ta = out["kernels"]["k_collect<9>"], out["kernels"]["k_absorb<9>"]

@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "conv_rows.h"
 #include "engine.h"
 
 using namespace tg;
@@ -58,7 +59,6 @@ struct Net {
     bool pol_att = false; AttW patt; ConvW head_a; std::string arch;
     float* bufQ = nullptr; float* hca = nullptr;   // q|k|v projections [rows][P][1.5F]; policy head conv output
     float* bufAct = nullptr;                       // pre-activated input of the next conv (DMA path)
-    int* tile_ctr = nullptr;                       // [2*NB] tile counters of the persistent conv launches (zeroed per forward)
     int prec = 0;                                  // cfg.net_precision: 0 = f32, 1 = fp16 storage + f32 accumulate (k_conv3x3_h2), 2 = 1 + fp16 residual stream,
                                                    // 3 = split precision ("f32x3"): every operand as fp16 hi + lo, three of the four products on the fp16 MFMA, f32 accumulate
     const float* head_g = nullptr; const float* head_ag = nullptr;   // [64][F] head conv weights for k_head_gemm (tap*6 + cout rows)
@@ -141,14 +141,17 @@ __global__ __launch_bounds__(256) void k_bits_to_rows(const uint32_t* __restrict
 // parameters therefore come from LDS (par = bias | s2 | t2, COUT floats each), and the residual is fetched one 4-tile chunk
 // ahead of the stores of the previous chunk, which turns ~CT*NPT serialized memory round trips into counted, overlapped ones.
 // EPI 0: relu(acc + bias)   EPI 1: acc + bias + res   EPI 2: acc + bias;   out2 (optional) = relu(v * s2 + t2).
-// SM / SM2: `out` / `out2` is a SLICE-MAJOR f32 tensor [COUT/16][M][16] (f32_sm_index) -- the layout the DMA-fed kernel reads its
-// inputs in: a slab piece (16 rows x 64 B) is then one contiguous KB, and so is what one store instruction here writes.
-__device__ __forceinline__ size_t f32_sm_index(int m, int c, int M) { return ((size_t)(c >> 4) * M + m) * 16 + (c & 15); }
+// SM / SM2: `out` / `out2` is a SLICE-MAJOR f32 tensor [COUT/16][Msm][16] (f32_sm_index) -- the layout the DMA-fed kernel reads its
+// inputs in, with BOARD-GROUPED rows (conv_rows.h): srow[t] = conv_sg_row(board, position) of natural row mrow[t], Msm =
+// conv_sg_rows(boards) the padded row count.  A B fragment of k_conv3x3_sg (one position, 16 boards, 64 B of one slice) is then one
+// contiguous KB.  The rows of the absent boards of the last group of 16 are never written (stale or uninitialised, NaN included):
+// they only ever feed MFMA columns of those same absent boards, which are never stored.
+__device__ __forceinline__ size_t f32_sm_index(int srow, int c, int Msm) { return ((size_t)(c >> 4) * Msm + srow) * 16 + (c & 15); }
 
 template <int COUT, int CT, int NPT, int EPI, bool SM = false, bool SM2 = false>
 __device__ __forceinline__ void conv_epilogue(f32x4 (&acc)[CT][NPT], const int (&mrow)[NPT], int M, int co_base, int kq,
                                               float* __restrict__ out, const float* __restrict__ res, float* __restrict__ out2,
-                                              const float* par) {
+                                              const float* par, const int (&srow)[NPT], int Msm) {
     constexpr int CH = CT % 4 == 0 ? 4 : CT % 3 == 0 ? 3 : CT % 2 == 0 ? 2 : 1;   // cout tiles per chunk
     constexpr int NCH = (CT / CH) * NPT;
     static_assert(CT % CH == 0, "chunking");
@@ -178,14 +181,14 @@ __device__ __forceinline__ void conv_epilogue(f32x4 (&acc)[CT][NPT], const int (
                 } else if (EPI == 1) {
                     v = v + r[c & 1][i];
                 }
-                *reinterpret_cast<f32x4*>(out + (SM ? f32_sm_index(mrow[t], co_base + col, M) : (size_t)mrow[t] * COUT + co_base + col)) = v;
+                *reinterpret_cast<f32x4*>(out + (SM ? f32_sm_index(srow[t], co_base + col, Msm) : (size_t)mrow[t] * COUT + co_base + col)) = v;
                 if (out2) {
                     const f32x4 sc = *reinterpret_cast<const f32x4*>(par + COUT + col);
                     const f32x4 sh = *reinterpret_cast<const f32x4*>(par + 2 * COUT + col);
                     f32x4 u;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { float w = v[e] * sc[e] + sh[e]; u[e] = w > 0.f ? w : 0.f; }
-                    *reinterpret_cast<f32x4*>(out2 + (SM2 ? f32_sm_index(mrow[t], co_base + col, M) : (size_t)mrow[t] * COUT + co_base + col)) = u;
+                    *reinterpret_cast<f32x4*>(out2 + (SM2 ? f32_sm_index(srow[t], co_base + col, Msm) : (size_t)mrow[t] * COUT + co_base + col)) = u;
                 }
             }
         }
@@ -332,10 +335,13 @@ __global__ __launch_bounds__(256, (NPT > 2 ? 2 : 1)) void k_conv3x3(const float*
         }
     }
     // D tile: row (lane>>4)*4 + r = cout, column lane&15 = position
-    int mrow[NPT];
+    int mrow[NPT], srow[NPT];
 #pragma unroll
-    for (int t = 0; t < NPT; ++t) mrow[t] = m0 + (wave * NPT + t) * 16 + j;
-    conv_epilogue<COUT, CT, NPT, EPI, false, SM2>(acc, mrow, M, 0, kq, out, res, out2, par);
+    for (int t = 0; t < NPT; ++t) {
+        mrow[t] = m0 + (wave * NPT + t) * 16 + j;
+        srow[t] = SM2 ? conv_sg_row(mrow[t] / P, mrow[t] % P, P) : mrow[t];
+    }
+    conv_epilogue<COUT, CT, NPT, EPI, false, SM2>(acc, mrow, M, 0, kq, out, res, out2, par, srow, conv_sg_rows(M / P, P));
 }
 
 // LDS pointer type of the LDS-DMA builtins; counted wait on the in-order vector-memory counter (loads, stores and LDS-DMA share it)
@@ -371,121 +377,125 @@ __device__ __forceinline__ void tg_dma_buffer(u32x4 rsrc, int voff_bytes, tg_lds
 // conflicted on every read (measured: SQ_LDS_BANK_CONFLICT = 49 % of SQ_LDS_IDX_ACTIVE).
 __device__ __forceinline__ int swz64(int row) { return ((row >> 2) & 1) << 1; }
 
-// k_conv3x3_sg at F=128: stages per barrier (ring = 2*NG slots of 8 KB); measured 2: 138.5, 3: 131.6, 4: 127.1 TFLOP/s
-constexpr int kSgStagesPerBarrier = 2;
-// ---- F->F 3x3 conv of the f32 tower (F = 128 / 256, attention-free; input already activated by its producer) -------------------
-// Implicit GEMM on v_mfma_f32_16x16x4_f32: D[cout][pos] += W[tap][cout][cin] * X[pos + tap][cin].  F = 128: workgroup = 4 waves =
-// 192 consecutive rows x all 128 couts (wave: 3 position x 8 cout tiles, 96 accumulator registers), <= 162 VGPRs and 34 KB of LDS,
-// so THREE workgroups share a CU (three waves per SIMD fill each other's bubbles) and 16384 leaves are exactly 9 rounds of the 768
-// resident slots.  F = 256: 128 rows x 256 couts (2 x 16 tiles), two workgroups per CU.
-// Stage g = (16-channel slice, tap).  A (weights): the stage's tile arrives by LDS-DMA from a stage-ordered copy of the weights
-// ([slice*9+tap][cout][16]) into a 4-slot ring, two stages per barrier, the next pair landing while this one is used; the LDS
-// image is XOR-swizzled at the source (swz64) so ds_read_b128 fragments are conflict-free.  B (activations): inputs are
-// slice-major, so a B fragment (16 rows x 64 B of one slice) is ONE contiguous KB in memory and every wave loads its own B
-// fragments straight from L2 into registers, a stage ahead (out-of-board taps and rows outside the batch get an out-of-range
-// buffer offset, i.e. zeros) -- no activation slab in LDS, no zero-row select.  Everything is at least a stage old when it is
-// waited for, so each stage simply ends with s_waitcnt vmcnt(0).  An earlier design staged the activations as LDS slabs
-// (k_conv3x3_sd, one barrier per stage, 53 KB): 1-3.5 % slower on every shape, removed.
-// NPT = position tiles per wave (rows per workgroup = 64*NPT).  F = 128 is built for 3 (192 rows, three workgroups per CU: the best
-// shape when the batch fills whole rounds of the 768 resident slots, e.g. exactly 16384 leaves = 9.0 rounds) and for 2 (128 rows,
-// four per CU, 1024 slots): in steady state a wave evaluates ~15.7 k leaves = 8.63 rounds of the first shape, whose partial last
-// round costs almost a full one; the host picks per launch whichever shape wastes less of its last round (+2 % in steady state).
-template <int S, int F, int EPI, int NPT_ = (F == 128 ? 3 : 2)>
-__global__ __launch_bounds__(256, (F == 128 ? (NPT_ == 3 ? 3 : 4) : 2)) void k_conv3x3_sg(const float* __restrict__ in, float* __restrict__ out,
+// ---- F->F 3x3 conv of the f32 tower (F = 128 / 256; input already activated by its producer) -----------------------------------
+// Implicit GEMM on v_mfma_f32_16x16x4_f32: D[cout][board] += W[tap][cout][cin] * X[board][pos + tap][cin].
+// Workgroup = ONE board position x 128 boards x all F couts: 4 waves x NPT = 2 tiles, a tile = that position on one group of 16
+// boards (the 16 columns of an MFMA; conv_rows.h has the row order that makes such a tile one contiguous KB per slice).  Which of
+// the nine taps fall on the board is therefore the same for the whole workgroup, and it walks ONLY those: 9 taps at the (S-2)^2
+// interior positions, 6 on an edge, 4 in a corner -- (3S-2)^2 of the 9*S*S (position, tap) pairs, 625 of 729 at 9x9 and 3025 of
+// 3249 at 19x19.  A tap off the board costs no weight DMA, no barrier, no fragment read and no MFMA (the row-ordered kernel this
+// replaced loaded zeros for it and multiplied by them: 14.3 % of its MFMAs at 9x9).  Every output element still accumulates its
+// on-board (slice, tap, k) terms in the same order, so results are those of the full walk (x + w*0 = x).
+// Stage k = (16-channel slice k / nt, the (k % nt)-th on-board tap), nt = 4 / 6 / 9, so F/16 * nt stages -- always an even count.
+// A (weights): the stage's tile arrives by LDS-DMA from a stage-ordered copy of the weights ([slice*9+tap][cout][16]) into a
+// 4-slot ring (slot = k % 4), two stages per barrier, the next pair landing while this one is used; the LDS image is XOR-swizzled
+// at the source (swz64) so ds_read_b128 fragments are conflict-free.  Stages per barrier at F = 128, measured on the row-ordered
+// kernel: 2: 138.5, 3: 131.6, 4: 127.1 TFLOP/s.  B (activations): every wave loads its own B fragments straight from L2 into
+// registers, a stage ahead; a tap is the wave-uniform shift of (dy*S + dx)*16 rows inside the board group.  Everything is at least
+// a stage old when it is waited for, so each stage simply ends with s_waitcnt vmcnt(0).
+// Boards past the batch: a wave none of whose groups exists skips its loads and MFMAs (it still feeds the weight ring and meets
+// the barriers); absent boards next to present ones are computed on whatever their never-written rows hold and never stored -- an
+// MFMA column depends on its own B column only.  The buffer resource ends with the padded tensor, so nothing is read past it.
+// Workgroups are numbered board range major, and inside a range longest walk first (conv_pos_of): the 81 (361) workgroups that
+// share one range's input are neighbours, and each XCD takes a contiguous run of them.
+// F = 128: 95 VGPRs and 34 KB of LDS, four workgroups per CU; F = 256: 159 VGPRs and 67 KB, two per CU.  Three tiles per wave
+// (192 boards, three workgroups per CU at F = 128), the better shape of the row-ordered kernel on full rounds, measured 4-7 %
+// slower here at 9x9 and 19x19: the walks differ in length, and four shorter waves per SIMD fill each other's gaps better.
+template <int S, int F, int EPI>
+__global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const float* __restrict__ in, float* __restrict__ out,
                                                                        const float* __restrict__ res, const float* __restrict__ Ws,
                                                                        const float* __restrict__ bias, float* __restrict__ out2,
-                                                                       const float* __restrict__ s2, const float* __restrict__ t2, int M,
-                                                                       int* __restrict__ ctr) {
+                                                                       const float* __restrict__ s2, const float* __restrict__ t2, int rows) {
     constexpr int P = S * S, CT = F / 16, CC = 16;
-    constexpr int NPT = NPT_, TM = 64 * NPT;
+    constexpr int NPT = 2, TB = 64 * NPT;                               // tiles per wave, boards per workgroup
     constexpr int WPW = CT / 4;
-    constexpr int NSL = F / CC, NST = NSL * 9, NG = kSgStagesPerBarrier, D = F == 128 ? 2 * NG : 4, NGS = D / 2, NGRP = NST / NGS;   // NGS stages per barrier, two groups resident
-    static_assert((F == 128 || F == 256) && NST % NGS == 0, "tile geometry");
+    constexpr int NSL = F / CC, D = 4;                                  // two stages per barrier, two pairs resident
+    static_assert((F == 128 || F == 256) && NSL % 2 == 0, "tile geometry");
     __shared__ __attribute__((aligned(16))) float ws[D][F * CC];
     __shared__ __attribute__((aligned(16))) float par[3 * F];
-    __shared__ int next_tile;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 15, kq = lane >> 4;
-    // XCD-aware tile order (one tile per workgroup, F = 128): workgroup b runs on XCD b % 8, so XCD x takes the CONTIGUOUS tile range
-    // [x * tpx, (x + 1) * tpx) -- neighbouring tiles share their halo rows through one L2 instead of fetching them into two
-    // (HBM reads 1.21x -> 1.12x (EPI 0) / 1.10x -> 1.05x (EPI 1) of the input bytes, time unchanged)
-    int bid = blockIdx.x;
-    if (F == 128) { const int tpx = ((int)gridDim.x + 7) >> 3; bid = (bid & 7) * tpx + (bid >> 3); }
-    int m0 = bid * TM;
-    if (m0 >= M) return;                                                // the grid is rounded up to a multiple of 8
+    // XCD-aware order: workgroup b runs on XCD b % 8, so XCD x takes the CONTIGUOUS run [x * tpx, (x + 1) * tpx) of the numbering
+    // above -- the workgroups that read one board range's input share one L2
+    const int tpx = ((int)gridDim.x + 7) >> 3;
+    const int bid = ((int)blockIdx.x & 7) * tpx + ((int)blockIdx.x >> 3);
+    const int nrange = (rows + TB - 1) / TB;
+    if (bid >= nrange * P) return;                                      // the grid is rounded up to a multiple of 8
+    const int range = bid / P;
+    const int p = conv_pos_of(bid - range * P, S);
+    const int M = rows * P, Msm = conv_sg_rows(rows, P);
     for (int i = tid; i < F; i += 256) { par[i] = bias[i]; par[F + i] = out2 ? s2[i] : 0.f; par[2 * F + i] = out2 ? t2[i] : 0.f; }
 
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, M * F * 4, 0x00020000);
+    // the workgroup's walk: nt on-board taps, packed 4 bits each; k / nt by a multiplication that is exact far beyond NSL * 9
+    const unsigned mask = conv_tap_mask(p, S);
+    const int nt = conv_tap_count(mask), nst = NSL * nt;
+    const unsigned long long taps = conv_tap_list(mask);
+    const int inv = nt == 9 ? 7282 : nt == 6 ? 10923 : 16384;           // ceil(65536 / nt)
+    auto stage = [&](int k, int* sl, int* tap) {
+        *sl = (k * inv) >> 16;
+        *tap = (int)(taps >> (4 * (k - *sl * nt))) & 15;
+    };
+
+    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in), 0, Msm * F * 4, 0x00020000);
     const int prow = lane >> 2, pchunk = (lane & 3) ^ swz64(lane >> 2);
-    auto dma_w = [&](int g) {
+    auto dma_w = [&](int k) {
+        int sl, tap;
+        stage(k, &sl, &tap);
+        const float* src = Ws + (size_t)(sl * 9 + tap) * (F * CC);
 #pragma unroll
         for (int i = 0; i < WPW; ++i) {
             const int pc = wave * WPW + i;
-            tg_dma_global(Ws + (size_t)g * (F * CC) + pc * 16 * CC, (prow * CC + pchunk * 4) * 4, (tg_lds_void*)(&ws[g % D][pc * 256]));
+            tg_dma_global(src + pc * 16 * CC, (prow * CC + pchunk * 4) * 4, (tg_lds_void*)(&ws[k & (D - 1)][pc * 256]));
         }
     };
-    // F = 256 runs persistent with a DYNAMIC tile list: the first gridDim.x tiles are the block indices, every further tile index
-    // comes from an atomic counter (fetched by one lane while the current tile computes, published through LDS behind the loop's
-    // barriers), so the dispatcher-like balance is kept while the next tile's first weights go out before the current tile's stores
-    // and its residual / first B fragments right after them (+1.2-1.7 %).  At F = 128 (shorter tiles, three workgroups per CU) the
-    // same loop costs 2 %, so there every workgroup takes exactly one tile.
-    constexpr bool PERSIST = F == 256;
-    const int ntiles = (M + TM - 1) / TM;
     const int aoff = j * CC + ((kq ^ swz64(j)) << 2);
-    unsigned vmask[NPT]; int boff[NPT];
+    const int grp0 = (range * 4 + wave) * NPT;                          // the wave's first board group
+    const bool active = grp0 * 16 < rows;                               // wave-uniform
+    const int boff = ((conv_sg_row(grp0 * 16 + j, p, P)) * CC + kq * 4) * 4;   // byte offset of this lane's 16 B inside slice 0, tile 0
     f32x4 acc[CT][NPT], b_cur[NPT], b_next[NPT];
-    auto load_b = [&](f32x4* b, int g) {
-        const int sl = g / 9, tap = g % 9;
-        const int soff = (sl * M + (tap / 3 - 1) * S + (tap % 3 - 1)) * (CC * 4);       // wave-uniform: slice base + tap shift
+    auto load_b = [&](f32x4* b, int k) {
+        int sl, tap;
+        stage(k, &sl, &tap);
+        const int ty = (tap * 11) >> 5;                                  // tap / 3
+        const int soff = (sl * Msm + ((ty - 1) * S + (tap - 3 * ty - 1)) * 16) * (CC * 4);   // wave-uniform: slice base + tap shift
 #pragma unroll
-        for (int t = 0; t < NPT; ++t) {
-            const int voff = ((vmask[t] >> tap) & 1) ? boff[t] + soff : 0x7ffffff0;    // masked: out of range = zeros
-            b[t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, voff, 0, 0));
-        }
+        for (int t = 0; t < NPT; ++t)                                    // the offset carries everything: the range check is on it
+            b[t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, (int)((unsigned)boff + (unsigned)soff + (unsigned)(t * (P * 16 * CC * 4))), 0, 0));
     };
-    auto tile_setup = [&]() {                                            // masks, accumulator start values and stage-0 fragments of tile m0
+#pragma unroll
+    for (int k = 0; k < D; ++k) dma_w(k);
+    if (active) {
 #pragma unroll
         for (int t = 0; t < NPT; ++t) {
-            const int m = m0 + (wave * NPT + t) * 16 + j;
-            unsigned mk = 0;
-            if (m < M) {
-                const int p = m % P, x = p % S, y = p / S;
-#pragma unroll
-                for (int tap = 0; tap < 9; ++tap) {
-                    const int yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
-                    if (yy >= 0 && yy < S && xx >= 0 && xx < S) mk |= 1u << tap;
-                }
-            }
-            vmask[t] = mk; boff[t] = (m * CC + kq * 4) * 4;              // byte offset of this lane's 16 B inside slice 0
+            const int b = (grp0 + t) * 16 + j;
+            const int m = b < rows ? b * P + p : M - 1;
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {                            // EPI 1: start from the residual (no loads behind the epilogue's stores)
                 acc[ct][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-                // always issued (rows past the batch re-read the last row; they are never stored): the wait at the loop head counts them
-                if (EPI == 1) acc[ct][t] = *reinterpret_cast<const f32x4*>(res + (size_t)(m < M ? m : M - 1) * F + ct * 16 + kq * 4);
+                // always issued (boards past the batch re-read the last row; they are never stored): the wait below counts them
+                if (EPI == 1) acc[ct][t] = *reinterpret_cast<const f32x4*>(res + (size_t)m * F + ct * 16 + kq * 4);
             }
         }
         load_b(b_cur, 0);
-    };
-#pragma unroll
-    for (int g = 0; g < D; ++g) dma_w(g);
-    tile_setup();
-    for (;;) {
-        if (PERSIST && tid == 0) next_tile = (int)gridDim.x + atomicAdd(ctr, 1);    // read by everybody after the loop's barriers
-        // The barrier must see the weight DMAs of the first stages landed (and, in a persistent walk, the previous tile's stores
-        // gone); the operations tile_setup() issued after them -- CT*NPT residual loads, NPT B fragments -- are the wave's youngest
-        // and are waited for by the compiler, one by one, in front of the MFMA that first needs each.
+        // The barrier must see the weight DMAs of the first stages landed; the operations issued after them -- CT*NPT residual
+        // loads, NPT B fragments -- are the wave's youngest and are waited for by the compiler, one by one, in front of the MFMA
+        // that first needs each.
         TG_VMCNT((EPI == 1 ? CT * NPT : 0) + NPT);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        TG_BARRIER();
+    } else {
+        TG_VMCNT(0);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    TG_BARRIER();
 
 #pragma unroll 1
-        for (int pp = 0; pp < NGRP; ++pp) {
+    for (int k0 = 0; k0 < nst; k0 += 2) {
 #pragma unroll
-            for (int h = 0; h < NGS; ++h) {
-                const int g = NGS * pp + h;
-                const float* wcur = ws[g % D];
-                if (g + 1 < NST) load_b(b_next, g + 1);
+        for (int h = 0; h < 2; ++h) {
+            const int k = k0 + h;
+            if (active) {
+                const float* wcur = ws[k & (D - 1)];
+                if (k + 1 < nst) load_b(b_next, k + 1);
                 __builtin_amdgcn_sched_barrier(0);                       // keep the loads HERE: hipcc sinks them to their use, a stage later
                 f32x4 a_cur = *reinterpret_cast<const f32x4*>(wcur + aoff);
 #pragma unroll
@@ -499,31 +509,23 @@ __global__ __launch_bounds__(256, (F == 128 ? (NPT_ == 3 ? 3 : 4) : 2)) void k_c
                             acc[ct][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[s4], b_cur[t][s4], acc[ct][t], 0, 0, 0);
                     a_cur = a_next;
                 }
-                TG_VMCNT(0);                                             // B fragments of stage g+1 (and any weight pieces): a stage old
 #pragma unroll
                 for (int t = 0; t < NPT; ++t) b_cur[t] = b_next[t];
             }
-            TG_BARRIER();                                                // group pp+1 has landed for everybody; the slots of group pp are free
-            if (NGS * (pp + 2) < NST) {
-#pragma unroll
-                for (int h = 0; h < NGS; ++h) dma_w(NGS * (pp + 2) + h);
-            }
+            TG_VMCNT(0);                                                 // B fragments of stage k+1 (and any weight pieces): a stage old
         }
-        int mrow[NPT];
-#pragma unroll
-        for (int t = 0; t < NPT; ++t) mrow[t] = m0 + (wave * NPT + t) * 16 + j;
-        const int next = PERSIST ? __builtin_amdgcn_readfirstlane(next_tile) : ntiles;     // written before the loop's first barrier
-        const bool more = next < ntiles;
-        if (more) {                                                      // every wave is past the last barrier: the ring is free
-#pragma unroll
-            for (int g = 0; g < D; ++g) dma_w(g);
-        }
-        conv_epilogue<F, CT, NPT, (EPI == 1 ? 2 : EPI), EPI == 0, true>(acc, mrow, M, 0, kq, out, res, out2, par);
-        if (!more) break;
-        m0 = next * TM;
-        tile_setup();
-        TG_BARRIER();                                                    // everybody has read next_tile before it is overwritten
+        TG_BARRIER();                                                    // the next pair has landed for everybody; this pair's slots are free
+        if (k0 + 4 < nst) { dma_w(k0 + 4); dma_w(k0 + 5); }
     }
+    if (!active) return;
+    int mrow[NPT], srow[NPT];
+#pragma unroll
+    for (int t = 0; t < NPT; ++t) {
+        const int b = (grp0 + t) * 16 + j;
+        mrow[t] = b < rows ? b * P + p : M;                              // M: not stored
+        srow[t] = conv_sg_row(b, p, P);
+    }
+    conv_epilogue<F, CT, NPT, (EPI == 1 ? 2 : EPI), EPI == 0, true>(acc, mrow, M, 0, kq, out, res, out2, par, srow, Msm);
 }
 
 // fp16 activation tensors are CHUNK-MAJOR: [channels/32 slices][4 chunks of 8 channels][M rows][8 halfs].  A slab DMA piece (64 rows
@@ -1557,7 +1559,7 @@ __global__ __launch_bounds__(256, 1) void k_attention_mfma(const float* __restri
                         *reinterpret_cast<h4*>(o16 + h16_index(m, c2 + 16, M)) = lo;
                     }
                 } else {
-                    if (out2) *reinterpret_cast<f32x4*>(out2 + f32_sm_index(m, c, M)) = u;
+                    if (out2) *reinterpret_cast<f32x4*>(out2 + f32_sm_index(conv_sg_row(b, p, P), c, conv_sg_rows(rows, P))) = u;
                 }
             }
         }
@@ -2082,7 +2084,8 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
     constexpr int WQ = F / 4 + F / 4 + F;             // q|k|v projection width
     const bool big = (long long)M * F * 4 >= (1ll << 31);
     Chain chain = n->path.chain;
-    if (chain == CHAIN_DMA && big) chain = CHAIN_F32;
+    // the DMA chain's slice-major tensors hold whole groups of 16 boards (conv_rows.h) and are addressed by 32-bit byte offsets
+    if (chain == CHAIN_DMA && (long long)conv_sg_rows(rows, P) * F * 4 >= (1ll << 31)) chain = CHAIN_F32;
     if (chain == CHAIN_SPLIT && big) TG_FAIL(ctx, TG_ERR_ARG, "split-precision path: rows * P * F * 4 bytes must stay below 2 GiB per activation buffer");
     if (chain == CHAIN_F16 && (long long)M * F * 2 >= (1ll << 31)) TG_FAIL(ctx, TG_ERR_ARG, "fp16 path: rows * P * F * 2 bytes must stay below 2 GiB per activation buffer");
     const bool h16 = chain == CHAIN_F16 || chain == CHAIN_SPLIT, x2 = chain == CHAIN_SPLIT;
@@ -2111,7 +2114,6 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
                 return;
             }
             if (chain == CHAIN_DMA) {
-                if (n->NB) (void)hipMemsetAsync(n->tile_ctr, 0, sizeof(int) * 2 * n->NB, st);     // dynamic tile counters of the conv launches
                 hipLaunchKernelGGL((k_conv3x3<S, 16, F, false, 0, 9, 2, true>), dim3(grid), dim3(256), 0, st, n->x0, x, nullptr, n->stem.w,
                                    n->stem.b, nullptr, nullptr, M, act ? n->bufAct : nullptr, sn, tn);
                 return;
@@ -2133,24 +2135,14 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
                 return;
             }
             if (chain == CHAIN_DMA) {
-                // tile shape per launch (F = 128): rows one full round of resident workgroups covers = 768 x 192 or 1024 x 128; take the
-                // shape whose rounded-up round count wastes fewer rows (ties: the larger tile)
-                bool small_tiles = false;
-                if constexpr (F == 128) {
-                    const long long r3 = 768LL * 192, r2 = 1024LL * 128;
-                    small_tiles = ((M + r2 - 1) / r2) * r2 < ((M + r3 - 1) / r3) * r3;
-                }
-                const int SD_TM = F == 128 ? (small_tiles ? 128 : 192) : 128;
-                const int ntile_sd = (M + SD_TM - 1) / SD_TM, slots_sd = F == 128 ? ntile_sd : 512;  // F=256: 2 resident workgroups x 256 CUs walk a dynamic tile list
-                int grid_sd = ntile_sd < slots_sd ? ntile_sd : slots_sd;
-                if (F == 128) grid_sd = (grid_sd + 7) / 8 * 8;                                      // XCD-contiguous tile order
-                int* const ctr = n->tile_ctr + 2 * ridx;                                            // zeroed by the stem
-                auto* k1 = small_tiles ? &k_conv3x3_sg<S, F, 0, 2> : &k_conv3x3_sg<S, F, 0>;
-                auto* k2 = small_tiles ? &k_conv3x3_sg<S, F, 1, 2> : &k_conv3x3_sg<S, F, 1>;
+                // one workgroup per (range of 128 boards, position), the count rounded up to the XCD-contiguous order's multiple of 8
+                const int grid_sd = ((rows + 127) / 128 * P + 7) / 8 * 8;
+                auto* k1 = &k_conv3x3_sg<S, F, 0>;
+                auto* k2 = &k_conv3x3_sg<S, F, 1>;
                 { ProfScope ps(n, st, conv_flops);
-                  hipLaunchKernelGGL(k1, dim3(grid_sd), dim3(256), 0, st, n->bufAct, n->bufH, nullptr, b.g1, b.c1.b, nullptr, nullptr, nullptr, M, ctr); }
+                  hipLaunchKernelGGL(k1, dim3(grid_sd), dim3(256), 0, st, n->bufAct, n->bufH, nullptr, b.g1, b.c1.b, nullptr, nullptr, nullptr, rows); }
                 { ProfScope ps(n, st, conv_flops);
-                  hipLaunchKernelGGL(k2, dim3(grid_sd), dim3(256), 0, st, n->bufH, out, x, b.g2, b.c2.b, act ? n->bufAct : nullptr, sn, tn, M, ctr + 1); }
+                  hipLaunchKernelGGL(k2, dim3(grid_sd), dim3(256), 0, st, n->bufH, out, x, b.g2, b.c2.b, act ? n->bufAct : nullptr, sn, tn, rows); }
                 return;
             }
         }
@@ -2504,7 +2496,9 @@ int tg_net_load_arch(tg_ctx* ctx, const char* arch_c, const float* blob, size_t 
         const size_t act = sizeof(float) * (size_t)rows_cap * P * F;
         TG_HIP(ctx, hipMalloc((void**)&n->bufA, act));
         TG_HIP(ctx, hipMalloc((void**)&n->bufB, act));
-        TG_HIP(ctx, hipMalloc((void**)&n->bufH, act));
+        // bufH and bufAct are slice-major in the DMA chain: whole groups of 16 boards (conv_rows.h), the padding never written
+        const size_t act_sm = sizeof(float) * (size_t)conv_sg_rows(rows_cap, (int)P) * F;
+        TG_HIP(ctx, hipMalloc((void**)&n->bufH, act_sm));
         TG_HIP(ctx, hipMalloc((void**)&n->x0, sizeof(float) * (size_t)rows_cap * P * 16));
         TG_HIP(ctx, hipMalloc((void**)&n->hc, sizeof(float) * (size_t)rows_cap * P * 16));
         TG_HIP(ctx, hipMalloc((void**)&n->own, sizeof(float) * (size_t)rows_cap * P));
@@ -2514,8 +2508,7 @@ int tg_net_load_arch(tg_ctx* ctx, const char* arch_c, const float* blob, size_t 
         if (any_att) TG_HIP(ctx, hipMalloc((void**)&n->bufQ, sizeof(float) * (size_t)rows_cap * P * Wq));
         if (pol) TG_HIP(ctx, hipMalloc((void**)&n->hca, sizeof(float) * (size_t)rows_cap * P * 16));
         const size_t wcopy = (size_t)(NB > 0 ? 2 * NB : 1) * 9 * F * F;
-        if (p.chain == CHAIN_DMA) TG_HIP(ctx, hipMalloc((void**)&n->bufAct, act));
-        if (p.chain == CHAIN_DMA) TG_HIP(ctx, hipMalloc((void**)&n->tile_ctr, sizeof(int) * (size_t)(NB > 0 ? 2 * NB : 1)));
+        if (p.chain == CHAIN_DMA) TG_HIP(ctx, hipMalloc((void**)&n->bufAct, act_sm));
         for (Net::WeightSet& w : n->sets) {
             TG_HIP(ctx, hipMalloc((void**)&w.blob, sizeof(float) * n_floats));
             TG_HIP(ctx, hipMalloc((void**)&w.head_g, sizeof(float) * 64 * (size_t)F));
@@ -2633,7 +2626,7 @@ void tg_net_destroy(tg_ctx* ctx) {
     if (!ctx || !ctx->eng || !ctx->eng->net) return;
     Net* n = ctx->eng->net;
     if (n->pending) (void)hipEventSynchronize(n->loaded);
-    void* ptrs[] = {n->bufA, n->bufB, n->bufH, n->x0, n->hc, n->own, n->bufQ, n->hca, n->bufAct, n->act16, n->h16, n->x0h, n->tile_ctr, n->range};
+    void* ptrs[] = {n->bufA, n->bufB, n->bufH, n->x0, n->hc, n->own, n->bufQ, n->hca, n->bufAct, n->act16, n->h16, n->x0h, n->range};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (Net::WeightSet& w : n->sets) { void* q[] = {w.blob, w.wstage, w.wh, w.stem_h, w.head_h, w.wsc, w.head_g, w.head_ag, w.att_h, w.att_sc, w.head_x2, w.head_x2sc}; for (void* p : q) if (p) (void)hipFree(p); }
     if (n->side) (void)hipStreamDestroy(n->side);
