@@ -59,8 +59,9 @@ typedef struct tg_config {
                                    residual stream; 2 = as 1 with the residual stream stored in fp16 too (a quarter less HBM traffic);
                                    3 = split precision, opt-in: every conv operand as fp16 hi + lo, three of the four partial products (lo*lo dropped) on the
                                    fp16 matrix cores, f32 accumulate and residual stream (fp32-level accuracy at 2.4-3.1x the
-                                   simulations/s).  1 and 2 take attention-free towers of 128 / 256 filters; 3 also takes
-                                   attention layers at 9x9 (the reference's MainNetwork), anything else is refused by tg_net_load */
+                                   simulations/s).  1 and 2 take towers of 128 / 256 filters; attention layers (the reference's
+                                   MainNetwork) are taken by 1 at 9x9 with 128 filters and by 3 at 9x9, never by 2; anything else is
+                                   refused by tg_net_load */
     int32_t record_games;       /* 1 (default): every game's move record -- env.encode(root) bit-packed, raw visit counts, side to
                                    move; the three Python lists of self_play.py:917-926 -- is kept in HBM for tg_sp_harvest */
     int32_t pool_slots;         /* tree memory: 32-byte slots provisioned PER GAME ON AVERAGE in the pool all games of the context share

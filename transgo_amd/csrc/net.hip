@@ -31,7 +31,7 @@ struct ConvW { const float* w; const float* b; };
 struct BlockW { const float* s1; const float* t1; ConvW c1; ConvW c2; const float* g1; const float* g2;
                 const _Float16* h1; const _Float16* h2; };   // g1/g2: stage-ordered f32, h1/h2: stage-ordered fp16 copies of c1.w / c2.w
 struct AttW { ConvW qkv; const float* gamma; const float* s; const float* t;          // Self_Attention, model.py:288-315
-              const _Float16* x3w = nullptr; const float* x3sc = nullptr; };          // split q|k|v weights (LDS image) + 2^-s of k_attention_x3
+              const _Float16* x3w = nullptr; const float* x3sc = nullptr; };          // q|k|v weights as the LDS image of k_attention_x3 (split, + 2^-s) / k_attention_h (fp16)
 struct Layer { int kind; int ridx; AttW a; };                                         // kind 0: residual block blocks[ridx]; 1: attention
 
 // Which forward runs, decided once at load (net_path) and read by the buffer allocation, the weight restaging and forward_t.
@@ -47,6 +47,7 @@ struct NetPath {
     Chain chain = CHAIN_F32;
     bool r16 = false;          // CHAIN_F16: fp16 residual stream too (net_precision 2)
     bool att_x3 = false;       // CHAIN_SPLIT: attention blocks on the fused k_attention_x3 (9x9, F = 128)
+    bool att_h = false;        // CHAIN_F16, f32 residual stream: attention blocks on the fused k_attention_h (9x9, F = 128)
     bool head_x2 = false;      // CHAIN_SPLIT: the head conv on k_head_gemm_x2 (F = 128, the trunk ends in a residual block)
     size_t att_lds = 0;        // k_attention's dynamic LDS in bytes; 0: no attention, or its image does not fit
 };
@@ -86,7 +87,7 @@ struct Net {
     struct WeightSet { float* blob = nullptr; float* wstage = nullptr; _Float16* wh = nullptr; _Float16* stem_h = nullptr; _Float16* head_h = nullptr;
                        float* wsc = nullptr; float* head_g = nullptr; float* head_ag = nullptr;
                        _Float16* att_h = nullptr; float* att_sc = nullptr;
-                       _Float16* head_x2 = nullptr; float* head_x2sc = nullptr; };                          // k_attention_x3: per attention layer, split weight image + scale   // head_g / head_ag: k_head_gemm copies of head / head_a
+                       _Float16* head_x2 = nullptr; float* head_x2sc = nullptr; };                          // att_h / att_sc: per attention layer, k_attention_x3's split weight image + scale, or k_attention_h's fp16 image (no scale)   // head_g / head_ag: k_head_gemm copies of head / head_a
     WeightSet sets[2]; int active = 0; bool pending = false;
     hipStream_t side = nullptr; hipEvent_t loaded = nullptr, swapped = nullptr; float* pinned = nullptr;
     // profiling of the dominant kernel (3x3 conv F->F) with HIP events on the launch stream
@@ -1970,6 +1971,315 @@ __global__ __launch_bounds__(256) void k_restage_att_split(const float* __restri
     }
 }
 
+// Self_Attention as ONE kernel for the fp16-storage chain (net_precision 1, F = 128, 9x9): k_attention_x3 with a single fp16 product
+// in the q/k/v projection.  What rounds to fp16 is the projection's input (x, under PRO relu(x*ps + pt)) and its weights; the biases,
+// q, k, v, the energy GEMM, the softmax, the output GEMM, gamma, the residual and the block's BN are f32 exactly as in
+// k_attention_x3, whose phases this kernel keeps.  What differs:
+//   * the weight image is [F/32 groups][W couts][32 halfs] of plain fp16 (k_restage_att_half; no scale), 48 KB, the 64-B rows
+//     XOR-swizzled by swz64(cout) as everywhere; one K = 32 step of v_mfma_f32_16x16x32_f16 covers 32 real channels;
+//   * lane (j, kq) loads channels g*32 + kq*4 .. +3 and g*32 + 16 + kq*4 .. +3 of row j (two 16-B loads) and rounds them once; its K
+//     slots kq*8 + e hold those eight in that order and the image's rows are stored in the same order.  With that order the lane's two
+//     loads ARE its elements of the two D tiles ct = 2g, 2g + 1 of column j (row = channel ct*16 + kq*4 + r): the residual goes from
+//     the row registers into the output accumulators with no shuffle (k_attention_x3 needs 32 ds_bpermute per row block);
+//   * the f32 biases start the projection accumulators.
+// Per board: 288 K=32 fp16 steps (96 for q^T / k^T, 6 x 32 for v) + 1296 f32 16x16x4 steps.  One workgroup of 4 waves per CU: the
+// output accumulators (192 registers) and q^T / k^T (96) alone are more than the 256 registers a second wave per SIMD would leave,
+// although two images (57 KB each with parameters and touch scratch) would fit the LDS.
+template <int S, int F, bool PRO>
+__global__ __launch_bounds__(256, 1) void k_attention_h(const float* __restrict__ xin, float* __restrict__ out, _Float16* __restrict__ out2,
+                                                        const _Float16* __restrict__ wimg, const float* __restrict__ qb,
+                                                        const float* __restrict__ gamma,
+                                                        const float* __restrict__ bs, const float* __restrict__ bt,
+                                                        const float* __restrict__ ps, const float* __restrict__ pt,
+                                                        const float* __restrict__ s2, const float* __restrict__ t2, int rows,
+                                                        unsigned* __restrict__ ovf) {
+    constexpr int P = S * S, FQ = F / 4, W = 2 * FQ + F, NT = (P + 15) / 16, CT = F / 16, NG = F / 32, NSUB = FQ / 16;
+    static_assert(P <= 96 && FQ % 16 == 0 && NG % 2 == 0 && NG * W * 64 + (W + 6 * F) * 4 + 4096 <= 65536, "attention tile geometry");
+    extern __shared__ __attribute__((aligned(16))) unsigned char att_smem[];
+    _Float16* const wl = reinterpret_cast<_Float16*>(att_smem);                       // [NG][W][32]
+    for (int i = threadIdx.x; i < NG * W * 4; i += 256) reinterpret_cast<f32x4*>(wl)[i] = reinterpret_cast<const f32x4*>(wimg)[i];
+    // per-channel parameters behind the image, as in k_attention_x3: q|k|v bias [W], bn scale / shift, next layer's bn scale / shift,
+    // prologue scale / shift [F each]
+    float* const prm = reinterpret_cast<float*>(att_smem + (size_t)NG * W * 64);
+    for (int i = threadIdx.x; i < W; i += 256) prm[i] = qb[i];
+    for (int i = threadIdx.x; i < F; i += 256) {
+        prm[W + i] = bs[i]; prm[W + F + i] = bt[i];
+        prm[W + 2 * F + i] = out2 ? s2[i] : 1.f; prm[W + 3 * F + i] = out2 ? t2[i] : 0.f;
+        prm[W + 4 * F + i] = PRO ? ps[i] : 1.f; prm[W + 5 * F + i] = PRO ? pt[i] : 0.f;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // scalar: board pointers stay in SGPRs
+    const int j = lane & 15, kq = lane >> 4;
+    const int wfo = j * 32 + ((kq ^ swz64(j)) << 3);                                 // this lane's 16-B chunk of weight row j
+    auto wgroup = [&](int g) { return wl + g * W * 32; };                            // (the whole image is within a ds_read's 16-bit offset)
+    const int M = rows * P;
+    // Addresses: tile t of a board starts 16 rows = 16*F floats further (a scalar add on the board pointer); within the tile lane j
+    // takes row j -- except in the last tile, where rows past the board clamp to its last row.  Channel kq*4 of the row serves the
+    // projection reads (+ g*128 B, + 64 B) and the D tiles of the epilogue (+ ct*64 B) alike.
+    constexpr int LASTR = P - 1 - (NT - 1) * 16;                                     // last valid row of the last tile
+    const unsigned eoA = (unsigned)j * F * 4u + kq * 16u, eoB = (unsigned)(j <= LASTR ? j : LASTR) * F * 4u + kq * 16u;
+    const unsigned hoA = ((unsigned)(kq >> 1) * M + j) * 16u + (kq & 1) * 8u;        // chunk-major fp16 output (h16_index), + t*256 per tile
+    auto tile = [](const float* board, int t) { return board + t * 16 * F; };
+    auto ld16 = [](const float* base, unsigned byte_off) { return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + byte_off); };
+    const float* l_ps = nullptr; const float* l_pt = nullptr;                          // set per board (LDS parameter block)
+    struct Pro { f32x4 sc[2], sh[2]; };                                               // prologue scale / shift of this lane's 8 channels of a group
+    auto pro_of = [&](int g) {
+        Pro p{};
+        if constexpr (PRO) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) { p.sc[h] = *reinterpret_cast<const f32x4*>(l_ps + g * 32 + h * 16 + kq * 4); p.sh[h] = *reinterpret_cast<const f32x4*>(l_pt + g * 32 + h * 16 + kq * 4); }
+        }
+        return p;
+    };
+    // range guard (see conv_epilogue_h8): the largest |x| this wave rounded in phase A (phase B rounds the same values again) and the
+    // largest value the epilogue rounds to fp16; checked once per board.  As in the conv epilogue, fmaxf drops a NaN operand: what is
+    // counted is a value beyond +-65504 (inf included), the event that first produces NaNs downstream -- a NaN that arrives is not
+    float amax = 0.f;
+    auto half8 = [&](const f32x4 (&src)[2], const Pro& pr, bool track = false) -> h8 {
+        h8 xf;
+#pragma unroll
+        for (int e = 0; e < 8; e += 2) {
+            f32x2 v = {src[e >> 2][e & 3], src[e >> 2][(e & 3) + 1]};
+            if constexpr (PRO) {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) { const float w = v[q] * pr.sc[e >> 2][(e & 3) + q] + pr.sh[e >> 2][(e & 3) + q]; v[q] = w > 0.f ? w : 0.f; }
+            }
+            if (track) amax = __builtin_fmaxf(amax, __builtin_fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])));
+            const h2 o = __builtin_convertvector(v, h2);
+            xf[e] = o[0]; xf[e + 1] = o[1];
+        }
+        return xf;
+    };
+    f32x4 rawA[NT][2], rawB[NT][2];                                                  // phase A stream: one group of all six tiles each
+    h8 xfA[NT], xfB[NT];
+    // (the lane offsets are made opaque where they are used, as in k_attention_x3: hoisted in their 64-bit form they are spilled)
+    auto issue = [&](const float* xb, int g, f32x4 (&dst)[NT][2]) {
+        unsigned oa = eoA, ob = eoB;
+        asm volatile("" : "+v"(oa), "+v"(ob));
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            dst[t][0] = ld16(tile(xb, t), (t + 1 < NT ? oa : ob) + g * 128);
+            dst[t][1] = ld16(tile(xb, t), (t + 1 < NT ? oa : ob) + g * 128 + 64);
+        }
+    };
+    auto round_group = [&](const f32x4 (&src)[NT][2], int g, h8 (&xf)[NT]) {
+        const Pro pr = pro_of(g);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) xf[t] = half8(src[t], pr, true);
+    };
+    int b = blockIdx.x * 4 + wave;
+    if (b >= rows) return;
+    { const float* xb0 = xin + (size_t)b * P * F; issue(xb0, 0, rawB); issue(xb0, 1, rawA); }
+    for (; b < rows; b += gridDim.x * 4) {
+        const float* xb = xin + (size_t)b * P * F;
+        // opaque per board: LDS is read-only from here on, so every parameter read would otherwise be hoisted out of the board loop
+        unsigned popq = 0;
+        asm volatile("" : "+v"(popq));                                                // (an opaque OFFSET: the pointer keeps its LDS address space)
+        const float* const l_qb = prm + popq;
+        const float* const l_bs = l_qb + W; const float* const l_bt = l_bs + F;
+        const float* const l_s2 = l_bt + F; const float* const l_t2 = l_s2 + F; l_ps = l_t2 + F; l_pt = l_ps + F;
+        // ---- phase A: q^T and k^T, [c][pos] tiles, the f32 bias in the accumulator ----
+        f32x4 qk[2 * NSUB][NT];
+#pragma unroll
+        for (int ct = 0; ct < 2 * NSUB; ++ct) {
+            const f32x4 bq = *reinterpret_cast<const f32x4*>(l_qb + ct * 16 + kq * 4);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) qk[ct][t] = bq;
+        }
+        auto mfma_qk = [&](int g, const h8 (&xf)[NT]) {
+#pragma unroll
+            for (int ct = 0; ct < 2 * NSUB; ++ct) {
+                const h8 a = *reinterpret_cast<const h8*>(wgroup(g) + ct * 16 * 32 + wfo);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) qk[ct][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, xf[t], qk[ct][t], 0, 0, 0);
+            }
+        };
+        round_group(rawB, 0, xfA);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int g = 0; g < NG; g += 2) {
+            if (g + 2 < NG) issue(xb, g + 2, rawB);
+            mfma_qk(g, xfA);
+            round_group(rawA, g + 1, xfB);
+            TG_ATT_SCHED(2 * NSUB * NT, 4);
+            if (g + 3 < NG) issue(xb, g + 3, rawA);
+            mfma_qk(g + 1, xfB);
+            if (g + 2 < NG) round_group(rawB, g + 2, xfA);
+            TG_ATT_SCHED(2 * NSUB * NT, 4);
+        }
+        // ---- phase B, block tm = rows i in [16 tm, 16 tm + 16) ----
+        f32x4 rv[NG][2];                                                             // the block's x rows, all groups
+        auto issue_rows = [&](int tm) {
+            unsigned o = tm + 1 < NT ? eoA : eoB;
+            asm volatile("" : "+v"(o));
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                rv[g][0] = ld16(tile(xb, tm), o + g * 128);
+                rv[g][1] = ld16(tile(xb, tm), o + g * 128 + 64);
+            }
+        };
+        issue_rows(0);
+        // The residual x (PRO: relu(x*ps + pt)) is ADDED INTO the output accumulators and v carries the factor gamma, so that they
+        // end as gamma * out + x and the epilogue has no loads at all (see k_attention_x3)
+        const float gam = gamma[0];
+        f32x4 acc[CT][NT];
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int tn = 0; tn < NT; ++tn) acc[ct][tn] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // next board's rows towards L2 now (one dword per 128-B line, as LDS-DMA into a scratch KB of this wave: results unused)
+        const int bnx = b + gridDim.x * 4;
+        const float* const xnext = xin + (size_t)(bnx < rows ? bnx : b) * P * F;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const unsigned lo = (unsigned)(lane + 64 * i) * 128u, off = lo < (unsigned)(P * F * 4 - 16) ? lo : (unsigned)(P * F * 4 - 16);
+            tg_dma_global(xnext, (int)off, (tg_lds_void*)(&att_smem[(size_t)NG * W * 64 + (W + 6 * F) * 4 + wave * 1024]));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int tm = 0; tm < NT; ++tm) {
+            // v for the block: D[pos][c], all channel tiles, the bias in the accumulator
+            f32x4 va[CT];
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) { const float bv = l_qb[2 * FQ + ct * 16 + j]; va[ct] = f32x4{bv, bv, bv, bv}; }
+            // weight fragments: eight in flight, each slot refilled (for the next group) right behind the MFMA that used it
+            h8 wf[CT];
+            auto wslot = [&](int g, int ct) { return *reinterpret_cast<const h8*>(wgroup(g) + (2 * FQ + ct * 16) * 32 + wfo); };
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) wf[ct] = wslot(0, ct);
+            h8 xf = half8(rv[0], pro_of(0)), xfn = xf;
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) {
+                    va[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf, wf[ct], va[ct], 0, 0, 0);
+                    if (g + 1 < NG) wf[ct] = wslot(g + 1, ct);
+                }
+                if (g + 1 < NG) xfn = half8(rv[g + 1], pro_of(g + 1));                  // next group's fragment, in the MFMA shadow
+#pragma unroll
+                for (int i_ = 0; i_ < CT; ++i_) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                xf = xfn;
+            }
+            // the residual rows of column tile tm: D tile ct = 2g + h (row = channel ct*16 + kq*4 + r, column = position tm*16 + j) is
+            // this lane's own rv[g][h] -- added now, before the next block's rows overwrite the registers
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+                f32x4 xv = rv[ct >> 1][ct & 1];
+                if constexpr (PRO) {
+                    const f32x4 vps = *reinterpret_cast<const f32x4*>(l_ps + ct * 16 + kq * 4), vpt = *reinterpret_cast<const f32x4*>(l_pt + ct * 16 + kq * 4);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) { const float w = xv[q] * vps[q] + vpt[q]; xv[q] = w > 0.f ? w : 0.f; }
+                }
+                acc[ct][tm] = acc[ct][tm] + xv;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (tm + 1 < NT) issue_rows(tm + 1);                                      // lands during the block's energy / output GEMMs
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) va[ct] = va[ct] * gam;
+            // energies of the block (exact f32): e[tn] = q[tm] . k[tn]
+            f32x4 e[NT];
+#pragma unroll
+            for (int tn = 0; tn < NT; ++tn) e[tn] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int sub = 0; sub < NSUB; ++sub)
+#pragma unroll
+                for (int s4 = 0; s4 < 4; ++s4)
+#pragma unroll
+                    for (int tn = 0; tn < NT; ++tn)
+                        e[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(qk[sub][tm][s4], qk[NSUB + sub][tn][s4], e[tn], 0, 0, 0);
+            // softmax over j (columns) for the rows i = tm*16 + kq*4 + r
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float mx = -INFINITY;
+#pragma unroll
+                for (int tn = 0; tn < NT; ++tn) if (tn * 16 + j < P) mx = e[tn][r] > mx ? e[tn][r] : mx;
+#pragma unroll
+                for (int o = 0; o < 4; ++o) { const float t = row16_step(mx, o); mx = t > mx ? t : mx; }
+                float sum = 0.f;
+#pragma unroll
+                for (int tn = 0; tn < NT; ++tn) {
+                    const float v = tn * 16 + j < P ? __expf(e[tn][r] - mx) : 0.f;
+                    e[tn][r] = v; sum += v;
+                }
+#pragma unroll
+                for (int o = 0; o < 4; ++o) sum += row16_step(sum, o);
+                const float inv = (tm * 16 + kq * 4 + r < P) ? 1.f / sum : 0.f;     // rows past the board contribute nothing below
+#pragma unroll
+                for (int tn = 0; tn < NT; ++tn) e[tn][r] *= inv;
+            }
+            // out[c][j] += v[i][c] attention[i][j]: k-step r covers rows i = tm*16 + kq*4 + r; of the last block only the steps that
+            // touch a row < P exist
+            constexpr int LASTS = P - (NT - 1) * 16, NS_LAST = LASTS < 4 ? LASTS : 4;
+            const int ns = tm + 1 < NT ? 4 : NS_LAST;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (r >= ns) continue;
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                    for (int tn = 0; tn < NT; ++tn)
+                        acc[ct][tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[ct][r], e[tn][r], acc[ct][tn], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // ---- epilogue.  D tile: row = channel ct*16 + kq*4 + r, column = position tn*16 + j.  Stores only: the next board's first
+        // two groups go out before the first store, and the residual is already inside the accumulators ----
+        {
+            issue(xnext, 0, rawB); issue(xnext, 1, rawA);                             // unconditional (last board: its own rows again)
+        }
+        char* const yb = reinterpret_cast<char*>(out + (size_t)b * P * F);
+        unsigned eoE = eoA, hoE = hoA;
+        asm volatile("" : "+v"(eoE), "+v"(hoE));
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) {
+            const int c = ct * 16 + kq * 4;
+            const f32x4 vbs = *reinterpret_cast<const f32x4*>(l_bs + c), vbt = *reinterpret_cast<const f32x4*>(l_bt + c);
+            const f32x4 vs2 = *reinterpret_cast<const f32x4*>(l_s2 + c), vt2 = *reinterpret_cast<const f32x4*>(l_t2 + c);
+            // fp16 output: element (m, c) of the chunk-major tensor = chunk plane c >> 3 = ct*2 + (kq >> 1), row m, half (kq & 1)*4
+            const size_t hplane = ((size_t)ct * 2 * M + (size_t)b * P) * 16;
+#pragma unroll
+            for (int tn = 0; tn < NT; ++tn) {
+                if (tn * 16 + j >= P) continue;
+                f32x4 y, u;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float w = acc[ct][tn][q] * vbs[q] + vbt[q];
+                    y[q] = w > 0.f ? w : 0.f;
+                    const float z = y[q] * vs2[q] + vt2[q];
+                    u[q] = z > 0.f ? z : 0.f;
+                }
+                *reinterpret_cast<f32x4*>(yb + tn * 16 * F * 4 + (eoE + ct * 64)) = y;
+                if (out2) {
+                    h4 o;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) { o[q] = (_Float16)u[q]; amax = __builtin_fmaxf(amax, u[q]); }
+                    *reinterpret_cast<h4*>(reinterpret_cast<char*>(out2) + hplane + (hoE + tn * 256)) = o;
+                }
+            }
+        }
+        if (__builtin_amdgcn_ballot_w64(!(amax <= 65504.f)) != 0) { if (lane == 0) atomicAdd(ovf, 1u); amax = 0.f; }
+    }
+    TG_VMCNT(0);                                                                     // the last board's touches and stores
+}
+
+// the LDS image of k_attention_h: dst[g][cout][32] = half(w[cout][g*32 + ch(kk)]), kk the logical K slot of the physical position (the
+// four 16-B chunks of a row XOR-swizzled by swz64(cout)), ch(kk) = (kk >> 2 & 1)*16 + (kk >> 3)*4 + (kk & 3): lane kq's slots
+// kq*8 .. +7 are the channels its two 16-B loads of x bring (kq*4 .. +3 and 16 + kq*4 .. +3)
+__global__ __launch_bounds__(256) void k_restage_att_half(const float* __restrict__ w, _Float16* __restrict__ dst, int W, int F) {
+    const int total = F / 32 * W * 32;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+        const int k = i & 31, r = (i >> 5) % W, g = (i >> 5) / W;
+        const int kk = (((k >> 3) ^ swz64(r)) << 3) + (k & 7);
+        dst[i] = (_Float16)w[(size_t)r * F + g * 32 + ((kk >> 2) & 1) * 16 + (kk >> 3) * 4 + (kk & 3)];
+    }
+}
+
 // Heads after the 3x3 head convs (hc[row][p][16]: channels 0-1 value/own, 2-5 policy; BN+ReLU already applied).
 // HR rows per workgroup (8 at 9x9, 2 at 19x19): the dense weights (fc_act alone is 4P x A floats = 106 KB at 9x9) are read once per workgroup and used
 // for all its rows -- with one row per workgroup the kernel moved 1.7 GB of L2 -> CU traffic per 16384 rows.  Every output is the
@@ -2162,7 +2472,16 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
                                    a.gamma, a.s, a.t, ps, pt, sn, tn, rows, n->range);
                 return 0;
             }
+            if (chain == CHAIN_F16 && n->path.att_h) {   // the same block with one fp16 product in the projection
+                constexpr int ldsh = (int)(sizeof(_Float16) * F / 32 * WQ * 32 + sizeof(float) * (WQ + 6 * F) + 4096);
+                const int nwg = (rows + 3) / 4 < 256 ? (rows + 3) / 4 : 256;
+                auto* k = ps ? &k_attention_h<S, F, true> : &k_attention_h<S, F, false>;
+                hipLaunchKernelGGL(k, dim3(nwg), dim3(256), ldsh, st, xin, xout, act ? n->act16 : nullptr, a.x3w, a.qkv.b,
+                                   a.gamma, a.s, a.t, ps, pt, sn, tn, rows, n->range);
+                return 0;
+            }
         }
+        if (chain == CHAIN_F16) return -1;               // (tg_net_load_arch admits fp16 attention only where k_attention_h is built)
         if (chain == CHAIN_F32 && !n->path.att_lds) return -1;
         // the fused q|k|v 1x1 projection on the matrix cores, then the per-board core
         auto* kq = ps ? &k_conv3x3<S, F, WQ, true, 2, 1> : &k_conv3x3<S, F, WQ, false, 2, 1>;
@@ -2310,8 +2629,9 @@ void bind_weights(Net* n, int k) {
     const size_t per = 9 * (size_t)F * F;
     int ri = 0, ai = 0;
     int n_att = pol ? 1 : 0; for (char c : trunk) n_att += c == 'A';
-    const size_t att_img = (size_t)F / 16 * Wq * 32;                  // halfs per attention layer (k_attention_x3's LDS image)
-    auto bind_x3 = [&](AttW& a) { if (w.att_h) { a.x3w = w.att_h + (size_t)ai * att_img; a.x3sc = w.att_sc + ai; } ++ai; };
+    // halfs per attention layer: k_attention_x3's LDS image (hi | lo per 16 channels), or k_attention_h's (plain fp16)
+    const size_t att_img = (size_t)F / (n->path.att_h ? 32 : 16) * Wq * 32;
+    auto bind_x3 = [&](AttW& a) { if (w.att_h) { a.x3w = w.att_h + (size_t)ai * att_img; if (w.att_sc) a.x3sc = w.att_sc + ai; } ++ai; };
     for (char c : trunk) {
         Layer L; L.kind = c == 'A'; L.ridx = -1; L.a = AttW{};
         if (c == 'R') {
@@ -2400,6 +2720,11 @@ int fill_weight_set(tg_ctx* ctx, Net* n, int k, const float* blob, hipStream_t s
         }
         hipLaunchKernelGGL(k_restage_half, dim3(256), dim3(256), 0, st, view.stem.w, view.stem_h, F, 16, 64, 32, 1);
         hipLaunchKernelGGL(k_restage_half, dim3(256), dim3(256), 0, st, view.head.w, view.head_h, 16, F, F, 32, 0);
+        if (p.att_h) {                                                                // fused attention layers: the fp16 q|k|v image, trunk and +P
+            for (const Layer& L : view.layers)
+                if (L.kind == 1) hipLaunchKernelGGL(k_restage_att_half, dim3(96), dim3(256), 0, st, L.a.qkv.w, const_cast<_Float16*>(L.a.x3w), F / 4 * 2 + F, F);
+            if (n->pol_att) hipLaunchKernelGGL(k_restage_att_half, dim3(96), dim3(256), 0, st, view.patt.qkv.w, const_cast<_Float16*>(view.patt.x3w), F / 4 * 2 + F, F);
+        }
         TG_HIP(ctx, hipGetLastError());
     } else if (p.chain == CHAIN_DMA) {
         // stage-ordered copy for k_conv3x3_sg, [slice*9 + tap][cout][16 channels of the slice], made on the device
@@ -2439,6 +2764,7 @@ NetPath net_path(int S, int F, int prec, const std::string& trunk, bool pol) {
     }
     p.r16 = prec == 2;
     p.att_x3 = prec == 3 && any_att && F == 128 && S == 9;
+    p.att_h = prec == 1 && any_att && F == 128 && S == 9;
     p.head_x2 = prec == 3 && F == 128 && !trunk.empty() && trunk.back() == 'R';
     const size_t lds = sizeof(float) * (P * Wq + P * (P + 1));
     p.att_lds = any_att && lds <= 160 * 1024 ? lds : 0;
@@ -2484,8 +2810,8 @@ int tg_net_load_arch(tg_ctx* ctx, const char* arch_c, const float* blob, size_t 
     const size_t P = (size_t)S * S, A = P + 1, Wq = (size_t)F / 4 * 2 + F;
     const bool any_att = pol || trunk.find('A') != std::string::npos;
     int NB = 0; for (char c : trunk) NB += c == 'R';
-    if (prec >= 1 && ((any_att && !(prec == 3 && S == 9)) || (F != 128 && F != 256)))
-        TG_FAIL(ctx, TG_ERR_ARG, "net_precision 1 / 2 (fp16 matrix cores) is built for attention-free towers with 128 or 256 filters; 3 (split precision) also takes attention layers at 9x9");
+    if (prec >= 1 && ((any_att && !(prec == 3 && S == 9) && !(prec == 1 && S == 9 && F == 128)) || (F != 128 && F != 256)))
+        TG_FAIL(ctx, TG_ERR_ARG, "net_precision 1 / 2 (fp16 matrix cores) is built for towers with 128 or 256 filters; attention layers are built for 1 (fp16 storage, f32 residual stream) at 9x9 with 128 filters and for 3 (split precision) at 9x9, not for 2, nor for 1 at 19x19 or with 256 filters");
     if (!n) {
         n = new Net();
         e->net = n;
@@ -2505,7 +2831,7 @@ int tg_net_load_arch(tg_ctx* ctx, const char* arch_c, const float* blob, size_t 
         TG_HIP(ctx, hipMalloc((void**)&n->range, sizeof(unsigned) * 4));
         TG_HIP(ctx, hipMemset(n->range, 0, sizeof(unsigned) * 4));
 
-        if (any_att) TG_HIP(ctx, hipMalloc((void**)&n->bufQ, sizeof(float) * (size_t)rows_cap * P * Wq));
+        if (any_att && !p.att_h) TG_HIP(ctx, hipMalloc((void**)&n->bufQ, sizeof(float) * (size_t)rows_cap * P * Wq));
         if (pol) TG_HIP(ctx, hipMalloc((void**)&n->hca, sizeof(float) * (size_t)rows_cap * P * 16));
         const size_t wcopy = (size_t)(NB > 0 ? 2 * NB : 1) * 9 * F * F;
         if (p.chain == CHAIN_DMA) TG_HIP(ctx, hipMalloc((void**)&n->bufAct, act_sm));
@@ -2529,6 +2855,10 @@ int tg_net_load_arch(tg_ctx* ctx, const char* arch_c, const float* blob, size_t 
                 TG_HIP(ctx, hipMalloc((void**)&w.att_h, sizeof(_Float16) * n_att * ((size_t)F / 16 * Wq * 32)));
                 TG_HIP(ctx, hipMalloc((void**)&w.att_sc, sizeof(float) * 2 * n_att));
             }
+            if (p.att_h) {                                                       // k_attention_h: plain fp16, 48 KB per layer
+                size_t n_att = pol ? 1 : 0; for (char c : trunk) n_att += c == 'A';
+                TG_HIP(ctx, hipMalloc((void**)&w.att_h, sizeof(_Float16) * n_att * ((size_t)F / 32 * Wq * 32)));
+            }
         }
         if (h16) {
             TG_HIP(ctx, hipMalloc((void**)&n->act16, x2 ? act : act / 2));     // split precision: hi + lo per element
@@ -2545,6 +2875,11 @@ int tg_net_load_arch(tg_ctx* ctx, const char* arch_c, const float* blob, size_t 
             const int lds3 = (int)(sizeof(_Float16) * (size_t)F / 16 * Wq * 32 + sizeof(float) * (Wq + 6 * (size_t)F) + 4096);
             TG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention_x3<9, 128, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds3));
             TG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention_x3<9, 128, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds3));
+        }
+        if (p.att_h) {
+            const int ldsh = (int)(sizeof(_Float16) * (size_t)F / 32 * Wq * 32 + sizeof(float) * (Wq + 6 * (size_t)F) + 4096);
+            TG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention_h<9, 128, false>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsh));
+            TG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention_h<9, 128, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsh));
         }
         if (p.att_lds) {
             hipError_t er = hipSuccess;
