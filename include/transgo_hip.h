@@ -60,7 +60,8 @@ typedef struct tg_config {
                                    3 = split precision, opt-in: every conv operand as fp16 hi + lo, three of the four partial products (lo*lo dropped) on the
                                    fp16 matrix cores, f32 accumulate and residual stream (fp32-level accuracy at 2.4-3.1x the
                                    simulations/s).  1 and 2 take towers of 128 / 256 filters; attention layers (the reference's
-                                   MainNetwork) are taken by 1 at 9x9 with 128 filters and by 3 at 9x9, never by 2; anything else is
+                                   MainNetwork) are taken by 0 at 9x9 (every width) and at 19x19 with 128 / 256 filters (k_attention_t), by 1 at
+                                   9x9 with 128 filters and by 3 at 9x9, never by 2, and by neither 1 nor 3 at 19x19; anything else is
                                    refused by tg_net_load */
     int32_t record_games;       /* 1 (default): every game's move record -- env.encode(root) bit-packed, raw visit counts, side to
                                    move; the three Python lists of self_play.py:917-926 -- is kept in HBM for tg_sp_harvest */
@@ -218,7 +219,8 @@ size_t tg_net_blob_floats(int board_size, int encode_dim, int filters, int block
 int tg_net_load(tg_ctx* ctx, const float* blob, size_t n_floats, int rows_cap);
 /* Same with an explicit layer program: one letter per trunk layer, 'R' = pre-activation ResidualBlock (model.py:238-248),
  * 'A' = Self_Attention (model.py:288-315), optional "+P" = attention in the policy head (model.py:72,106).  The shipped
- * MainNetwork (model.py:49-76) is "RARRRARRRRAR+P"; tg_net_load uses cfg.net_blocks x 'R'.  Attention needs 9x9. */
+ * MainNetwork (model.py:49-76) is "RARRRARRRRAR+P"; tg_net_load uses cfg.net_blocks x 'R'.  Attention is built at 9x9, and in f32 (net_precision 0) at 19x19 with 128 or 256
+ * filters; the fp16 and split-precision modes with attention at 19x19 are refused at the load. */
 size_t tg_net_blob_floats_arch(int board_size, int encode_dim, int filters, const char* arch);
 int tg_net_load_arch(tg_ctx* ctx, const char* arch, const float* blob, size_t n_floats, int rows_cap);
 /* Weight refresh that never stalls a search (the hand-off of trainer.py:76-79 -> self_play.py:913): there are two complete

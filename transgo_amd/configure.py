@@ -20,13 +20,14 @@ class Config:
         self.input_dim = self.encode_state_channels
         self.num_features = 128                  # configure.py:37
         self.num_blocks = 6                      # tower depth (BASELINE.json "N-block x F-filter")
-        self.network = "tower"                   # "tower" | "transgo" (the shipped MainNetwork with attention, model.py:49-76)
+        self.network = "tower"                   # "tower" | "transgo" (the shipped MainNetwork with attention, model.py:49-76; at
+                                                 # board_size 19 in inference_dtype "f32" with 128 or 256 filters)
         self.concurrent_games = 4096             # boards resident on one GPU
         self.game_groups = 1                     # K > 1: the boards of a GPU as K independent groups on their own HIP streams (GroupedSelfPlay)
         self.stagger_games = 0                   # T > 1: slot g starts its first game at step g mod T (BatchedSelfPlay.start): games end
                                                  # spread over T steps instead of all on one; 0 = all slots start together
         self.inference_dtype = "f32"             # "f16": fp16 weights/activations, f32 accumulate (BASELINE config 5; towers of 128/256
-                                                 # filters, and network = "transgo" at 9x9 with 128 filters); "f16r" (attention-free
+                                                 # filters, and network = "transgo" at 9x9 with 128 filters, not at 19x19); "f16r" (attention-free
                                                  # towers only): the residual stream in fp16 as well (+4-6 %, error < 4e-4 over 40 blocks);
                                                  # "f32x3": split precision -- conv operands as fp16 hi + lo, f32 accumulate, ~1e-6 of f32
         self.batch_size = 2048

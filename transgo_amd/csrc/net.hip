@@ -35,7 +35,7 @@ struct AttW { ConvW qkv; const float* gamma; const float* s; const float* t;    
 struct Layer { int kind; int ridx; AttW a; };                                         // kind 0: residual block blocks[ridx]; 1: attention
 
 // Which forward runs, decided once at load (net_path) and read by the buffer allocation, the weight restaging and forward_t.
-//   CHAIN_F32   general f32 chain: k_conv3x3 everywhere (F = 32 / 64, 19x19 attention archs, TG_DMA_CONV=0, and the DMA
+//   CHAIN_F32   general f32 chain: k_conv3x3 everywhere (F = 32 / 64, TG_DMA_CONV=0, and the DMA
 //               chain's batches of 2 GiB or more per activation buffer)
 //   CHAIN_DMA   f32 tower of 128 / 256 filters on the DMA-fed k_conv3x3_sg; every producer also writes relu(bn1_next(.))
 //               slice-major for a residual block that follows, so the F->F kernels never activate anything
@@ -1570,6 +1570,190 @@ __global__ __launch_bounds__(256, 1) void k_attention_mfma(const float* __restri
     }
 }
 
+// The Self_Attention core TILED, for 19x19 (P = 361 = 22 tiles of 16 + 9 positions; F = 128, 256), exact f32 on the 16x16x4 MFMA:
+// ONE WORKGROUP (4 waves) PER BOARD.  The P x P energy matrix (521 KB) never exists; because the softmax normalises the index that
+// GEMM 2 SUMS over (see k_attention), no online rescaling is needed, but the row statistics must be complete before the first
+// output column is formed -- two passes over the energies:
+//   stage    k of the board into LDS, in B-fragment order [j tile][16-channel slice][lane] (one conflict-free 16-B read per lane and
+//            slice; rows >= P zero).  q is read from memory as A fragments (an i tile's are FQ/4 registers), v is streamed.
+//   pass 1   wave w takes the i tiles w, w+4, ..: the 23 energy tiles of the tile row in registers, m_i = max_j e_ij and
+//            1 / sum_j exp(e_ij - m_i) over the columns j < P (in-register + DPP row reduction, as k_attention_mfma), two floats per
+//            row into LDS; rows >= P get 1/l = 0.
+//   pass 2   for each i tile: the four waves recompute a quarter of the tile row each (bit-identical energies: same MFMA order),
+//            p_ij = exp(e_ij - m_i) / l_i (0 in padded rows and columns), and park the tiles in LDS AS THEY LIE in the D layout,
+//            which is the B-operand layout of GEMM 2 -- 16 B per lane, written and read back without conflicts (two buffers of
+//            23 KB, one barrier per i tile).  Every wave then feeds all 23 tiles to out[c][j] += v[i][c] p_ij for ITS 32 channels
+//            (2 channel tiles x 23 j tiles = 184 accumulator registers; the channels are split over the waves and, at F = 256,
+//            over two such sweeps, the second of which recomputes the probabilities).  v: 4 B per lane and k-step, 64-B runs, each
+//            element read once per board, requested one i tile ahead.
+//   epilogue y = relu(bn(gamma * out + x)) row-major and, for a residual block of the DMA-fed chain that follows, relu(bn1_next(y))
+//            slice-major in board-grouped rows (out2), exactly as k_attention_mfma<.., false> writes them.
+// MFMA instructions per board: F = 128 4232 (pass 1) + 4232 + 16928 (pass 2); F = 256 8464 + 2 x (8464 + 16928).
+// Resources (gfx950, scratch 0, one wave per SIMD): F = 128 234 VGPRs + 188 AGPRs, 97 152 B of dynamic LDS (k 47 104, tiles 47 104,
+// statistics 2 944); F = 256 256 VGPRs + 254 AGPRs, 144 256 B (k 94 208).
+template <int S, int F> constexpr int att_t_lds() {
+    constexpr int NT = (S * S + 15) / 16;
+    return (int)sizeof(float) * (4 * 64 * (NT * (F / 64) + 2 * NT) + 2 * NT * 16);
+}
+template <int S, int F>
+__global__ __launch_bounds__(256, 1) void k_attention_t(const float* __restrict__ qkv, const float* __restrict__ xin,
+                                                     float* __restrict__ out, float* __restrict__ out2,
+                                                     const float* __restrict__ gamma, const float* __restrict__ bs,
+                                                     const float* __restrict__ bt, const float* __restrict__ ps,
+                                                     const float* __restrict__ pt, const float* __restrict__ s2,
+                                                     const float* __restrict__ t2, int rows) {
+    constexpr int P = S * S, FQ = F / 4, W = 2 * FQ + F, NT = (P + 15) / 16, NSUB = FQ / 16, CT = F / 16, CPW = 2, NPASS = CT / (4 * CPW);
+    static_assert(FQ % 16 == 0 && CT % (4 * CPW) == 0, "attention tile geometry");
+    extern __shared__ float sm[];
+    f32x4* const kl = reinterpret_cast<f32x4*>(sm);                 // [NT][NSUB][64 lanes]: k as B fragments
+    f32x4* const pl = kl + NT * NSUB * 64;                          // [2][NT][64 lanes]: the probability tiles of one i tile
+    float* const rm = reinterpret_cast<float*>(pl + 2 * NT * 64);   // [NT * 16] row maxima
+    float* const ri = rm + NT * 16;                                 // [NT * 16] 1 / row sums, 0 in the padded rows
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 15, kq = lane >> 4;
+    const int b = blockIdx.x;
+    if (b >= rows) return;
+    const float* base = qkv + (size_t)b * P * W;
+    for (int e = threadIdx.x; e < NT * 16 * (FQ / 4); e += 256) {
+        const int p = e / (FQ / 4), c4 = e % (FQ / 4);              // position, quad of channels: slice c4 >> 2, k group c4 & 3
+        f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (p < P) v = *reinterpret_cast<const f32x4*>(base + (size_t)p * W + FQ + c4 * 4);
+        kl[((p >> 4) * NSUB + (c4 >> 2)) * 64 + (c4 & 3) * 16 + (p & 15)] = v;
+    }
+    __syncthreads();
+    // A fragments of q for the i tile `it` (padded rows repeat the last one; their probabilities are zeroed), and one energy tile
+    auto load_q = [&](int it, f32x4 (&qa)[NSUB]) {
+        const int row = it * 16 + j < P ? it * 16 + j : P - 1;
+#pragma unroll
+        for (int sub = 0; sub < NSUB; ++sub) qa[sub] = *reinterpret_cast<const f32x4*>(base + (size_t)row * W + sub * 16 + kq * 4);
+    };
+    auto energy = [&](const f32x4 (&qa)[NSUB], int jt) {
+        f32x4 e = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int sub = 0; sub < NSUB; ++sub) {
+            const f32x4 kb = kl[(jt * NSUB + sub) * 64 + lane];
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) e = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[sub][s4], kb[s4], e, 0, 0, 0);
+        }
+        return e;
+    };
+    // ---- pass 1: row statistics.  Lane (j, kq) holds rows it*16 + kq*4 + r, columns jt*16 + j of the tile row ----
+#pragma unroll 1
+    for (int it = wave; it < NT; it += 4) {
+        f32x4 qa[NSUB];
+        load_q(it, qa);
+        f32x4 e[NT];
+#pragma unroll
+        for (int jt = 0; jt < NT; ++jt) e[jt] = energy(qa, jt);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float mx = -INFINITY;
+#pragma unroll
+            for (int jt = 0; jt < NT; ++jt) if (jt * 16 + j < P) mx = e[jt][r] > mx ? e[jt][r] : mx;
+#pragma unroll
+            for (int o = 0; o < 4; ++o) { const float t = row16_step(mx, o); mx = t > mx ? t : mx; }
+            float sum = 0.f;
+#pragma unroll
+            for (int jt = 0; jt < NT; ++jt) sum += jt * 16 + j < P ? __expf(e[jt][r] - mx) : 0.f;
+#pragma unroll
+            for (int o = 0; o < 4; ++o) sum += row16_step(sum, o);
+            const int i = it * 16 + kq * 4 + r;
+            if (j == 0) { rm[i] = i < P ? mx : 0.f; ri[i] = i < P ? 1.f / sum : 0.f; }
+        }
+    }
+    __syncthreads();
+    // ---- pass 2: probabilities by i tile through LDS, GEMM 2 on this wave's channels, epilogue ----
+    const float g = gamma[0];
+    const float* vb = base + 2 * FQ;
+#pragma unroll 1
+    for (int pass = 0; pass < NPASS; ++pass) {
+        const int c0 = (pass * 4 + wave) * CPW;                      // first of this wave's channel tiles
+        // k-step kk of i tile `it` covers row i = it*16 + kq*4 + kk (the D row of the probability tile's register kk)
+        auto load_v = [&](int it, float (&dst)[CPW][4]) {
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                const int i = it * 16 + kq * 4 + kk;
+                const int ic = i < P ? i : P - 1;                        // the matching probabilities are zero
+#pragma unroll
+                for (int cp = 0; cp < CPW; ++cp) dst[cp][kk] = vb[(size_t)ic * W + (c0 + cp) * 16 + j];
+            }
+        };
+        f32x4 acc[CPW][NT];
+#pragma unroll
+        for (int cp = 0; cp < CPW; ++cp)
+#pragma unroll
+            for (int jt = 0; jt < NT; ++jt) acc[cp][jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        float av[CPW][4], an[CPW][4];
+        load_v(0, av);
+#pragma unroll 1
+        for (int it = 0; it < NT; ++it) {
+            f32x4 qa[NSUB];
+            load_q(it, qa);
+            const f32x4 m4 = *reinterpret_cast<const f32x4*>(rm + it * 16 + kq * 4);
+            const f32x4 i4 = *reinterpret_cast<const f32x4*>(ri + it * 16 + kq * 4);
+            f32x4* const pb = pl + (it & 1) * NT * 64;
+#pragma unroll 1
+            for (int jt = wave; jt < NT; jt += 4) {
+                f32x4 e = energy(qa, jt);
+                const bool col = jt * 16 + j < P;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) e[r] = col && it * 16 + kq * 4 + r < P ? __expf(e[r] - m4[r]) * i4[r] : 0.f;
+                pb[jt * 64 + lane] = e;
+            }
+#pragma unroll
+            for (int cp = 0; cp < CPW; ++cp)
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) an[cp][kk] = av[cp][kk];
+            if (it + 1 < NT) load_v(it + 1, an);
+            // one barrier per i tile: the tiles written next go to the other buffer, which every wave finished reading before it
+            // arrived here
+            __syncthreads();
+#pragma unroll
+            for (int jt = 0; jt < NT; ++jt) {
+                const f32x4 pr = pb[jt * 64 + lane];
+#pragma unroll
+                for (int cp = 0; cp < CPW; ++cp)
+#pragma unroll
+                    for (int kk = 0; kk < 4; ++kk)
+                        acc[cp][jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[cp][kk], pr[kk], acc[cp][jt], 0, 0, 0);
+            }
+#pragma unroll
+            for (int cp = 0; cp < CPW; ++cp)
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) av[cp][kk] = an[cp][kk];
+        }
+        // D tile: row = channel (c0+cp)*16 + kq*4 + r, column = position jt*16 + j
+#pragma unroll
+        for (int cp = 0; cp < CPW; ++cp) {
+            const int c = (c0 + cp) * 16 + kq * 4;
+            const f32x4 one = f32x4{1.f, 1.f, 1.f, 1.f}, zero = f32x4{0.f, 0.f, 0.f, 0.f};
+            const f32x4 vbs = *reinterpret_cast<const f32x4*>(bs + c), vbt = *reinterpret_cast<const f32x4*>(bt + c);
+            const f32x4 vps = ps ? *reinterpret_cast<const f32x4*>(ps + c) : one, vpt = ps ? *reinterpret_cast<const f32x4*>(pt + c) : zero;
+            const f32x4 vs2 = out2 ? *reinterpret_cast<const f32x4*>(s2 + c) : one, vt2 = out2 ? *reinterpret_cast<const f32x4*>(t2 + c) : zero;
+#pragma unroll
+            for (int jt = 0; jt < NT; ++jt) {
+                const int p = jt * 16 + j;
+                if (p >= P) continue;
+                const size_t m = (size_t)b * P + p;
+                const f32x4 x = *reinterpret_cast<const f32x4*>(xin + m * F + c);
+                f32x4 y, u;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    float xv = x[q];
+                    if (ps) { xv = xv * vps[q] + vpt[q]; xv = xv > 0.f ? xv : 0.f; }
+                    const float w = (g * acc[cp][jt][q] + xv) * vbs[q] + vbt[q];
+                    y[q] = w > 0.f ? w : 0.f;
+                    const float z = y[q] * vs2[q] + vt2[q];
+                    u[q] = z > 0.f ? z : 0.f;
+                }
+                *reinterpret_cast<f32x4*>(out + m * F + c) = y;
+                if (out2) *reinterpret_cast<f32x4*>(out2 + f32_sm_index(conv_sg_row(b, p, P), c, conv_sg_rows(rows, P))) = u;
+            }
+        }
+        if (pass + 1 < NPASS) __syncthreads();                       // the next sweep starts in the buffer the last i tile used
+    }
+}
+
 // Self_Attention as ONE kernel for the split-precision chain (net_precision 3, F = 128, 9x9): the q/k/v 1x1 projection is computed
 // inside the per-board core, on the fp16 matrix cores in split precision, and never goes through memory (the two-kernel form
 // moves 62 KB of q|k|v per board out and back in: at 16 k boards the pair took 0.61 + 0.70 ms, 23 % of a MainNetwork wave).
@@ -2482,10 +2666,18 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
             }
         }
         if (chain == CHAIN_F16) return -1;               // (tg_net_load_arch admits fp16 attention only where k_attention_h is built)
-        if (chain == CHAIN_F32 && !n->path.att_lds) return -1;
+        if (S != 19 && chain == CHAIN_F32 && !n->path.att_lds) return -1;
         // the fused q|k|v 1x1 projection on the matrix cores, then the per-board core
         auto* kq = ps ? &k_conv3x3<S, F, WQ, true, 2, 1> : &k_conv3x3<S, F, WQ, false, 2, 1>;
         hipLaunchKernelGGL(kq, dim3(grid), dim3(256), 0, st, xin, n->bufQ, nullptr, a.qkv.w, a.qkv.b, ps, pt, M, nullptr, nullptr, nullptr);
+        // 19x19 (f32, both f32 chains): the tiled core, one workgroup per board; `act` is set in the DMA chain only
+        if constexpr (S == 19) {
+            if (x2) return -1;
+            constexpr int ldst = att_t_lds<S, F>();
+            hipLaunchKernelGGL((k_attention_t<S, F>), dim3(rows), dim3(256), ldst, st, n->bufQ, xin, xout,
+                               act ? n->bufAct : nullptr, a.gamma, a.s, a.t, ps, pt, sn, tn, rows);
+            return 0;
+        } else {
         // the MFMA core, one wave per board, writes the next residual block's input too (split: as hi + lo)
         if constexpr (S == 9 && F == 256) {
             if (x2) {
@@ -2503,6 +2695,7 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
         }
         hipLaunchKernelGGL((k_attention<S, F>), dim3(rows), dim3(256), n->path.att_lds, st, n->bufQ, xin, xout, a.gamma, a.s, a.t, ps, pt);
         return 0;
+        }
     };
     // head conv F -> 16 (6 real couts) on relu(bn(in)) (ps/pt) or on in: GEMM + col2im (k_head_gemm); TG_HEAD_GEMM=0 selects the
     // implicit-GEMM kernel it replaced
@@ -2535,7 +2728,7 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
         const Layer& L = n->layers[i];
         const bool act = next_bn(i + 1, &sn, &tn);
         if (L.kind == 1) {
-            if (attention(L.a, x, y, nullptr, nullptr, act, sn, tn)) TG_FAIL(ctx, TG_ERR_ARG, "attention blocks need P*(1.5F+P+1) floats of LDS: not available at this board size");
+            if (attention(L.a, x, y, nullptr, nullptr, act, sn, tn)) TG_FAIL(ctx, TG_ERR_ARG, "attention blocks: no kernel for this shape and precision (built: f32 at 9x9 with 32 / 64 / 128 / 256 filters and at 19x19 with 128 / 256, f16 at 9x9 with 128, f32x3 at 9x9 with 128 / 256)");
         } else {
             // nothing reads the last block's f32 stream when the head conv takes act16 and no policy attention follows
             block(n->blocks[L.ridx], L.ridx, i + 1 == nl && head16 && !n->pol_att ? nullptr : y, act, sn, tn);
@@ -2559,7 +2752,7 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
     if (n->pol_att) {
         // the f32 head conv reads the attention's f32 output in the split chain too (the policy head conv on the split MFMA was
         // measured: what it saves the attention block's extra split write of its output costs -- 723.3 vs 723.2 k sims/s)
-        if (attention(n->patt, x, y, n->s_end, n->t_end, false, nullptr, nullptr)) TG_FAIL(ctx, TG_ERR_ARG, "attention policy head: not enough LDS at this board size");
+        if (attention(n->patt, x, y, n->s_end, n->t_end, false, nullptr, nullptr)) TG_FAIL(ctx, TG_ERR_ARG, "attention policy head: no kernel for this shape and precision (built: f32 at 9x9 with 32 / 64 / 128 / 256 filters and at 19x19 with 128 / 256, f16 at 9x9 with 128, f32x3 at 9x9 with 128 / 256)");
         head_conv(y, n->hca, n->head_ag, n->head_a, nullptr, nullptr);
         hca = n->hca;
     }
@@ -2758,7 +2951,7 @@ NetPath net_path(int S, int F, int prec, const std::string& trunk, bool pol) {
     NetPath p;
     if (prec == 3) p.chain = CHAIN_SPLIT;
     else if (prec >= 1) p.chain = CHAIN_F16;
-    else if ((F == 128 || F == 256) && (!any_att || S == 9)) {          // attention layers need the 9x9 MFMA kernel
+    else if (F == 128 || F == 256) {                                    // attention layers: k_attention_mfma (9x9), k_attention_t (19x19)
         const char* dma = getenv("TG_DMA_CONV");
         p.chain = dma && atoi(dma) == 0 ? CHAIN_F32 : CHAIN_DMA;
     }
@@ -2812,6 +3005,8 @@ int tg_net_load_arch(tg_ctx* ctx, const char* arch_c, const float* blob, size_t 
     int NB = 0; for (char c : trunk) NB += c == 'R';
     if (prec >= 1 && ((any_att && !(prec == 3 && S == 9) && !(prec == 1 && S == 9 && F == 128)) || (F != 128 && F != 256)))
         TG_FAIL(ctx, TG_ERR_ARG, "net_precision 1 / 2 (fp16 matrix cores) is built for towers with 128 or 256 filters; attention layers are built for 1 (fp16 storage, f32 residual stream) at 9x9 with 128 filters and for 3 (split precision) at 9x9, not for 2, nor for 1 at 19x19 or with 256 filters");
+    if (prec == 0 && any_att && S == 19 && F != 128 && F != 256)
+        TG_FAIL(ctx, TG_ERR_ARG, "attention layers at 19x19 are built for net_precision 0 (f32) with 128 or 256 filters (k_attention_t); at 9x9 for every filter count of the f32 path");
     if (!n) {
         n = new Net();
         e->net = n;
@@ -2880,6 +3075,12 @@ int tg_net_load_arch(tg_ctx* ctx, const char* arch_c, const float* blob, size_t 
             const int ldsh = (int)(sizeof(_Float16) * (size_t)F / 32 * Wq * 32 + sizeof(float) * (Wq + 6 * (size_t)F) + 4096);
             TG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention_h<9, 128, false>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsh));
             TG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention_h<9, 128, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsh));
+        }
+        if (any_att && prec == 0 && S == 19) {            // k_attention_t: k fragments, two probability tile rows, row statistics
+            hipError_t er = hipSuccess;
+            if (F == 128) er = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention_t<19, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, att_t_lds<19, 128>());
+            if (F == 256) er = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention_t<19, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, att_t_lds<19, 256>());
+            TG_HIP(ctx, er);
         }
         if (p.att_lds) {
             hipError_t er = hipSuccess;

@@ -168,8 +168,9 @@ def weight_range(blob, net_precision=0):
 # tg_config.net_precision: "f16" = fp16 weights/activations in HBM and LDS with f32 accumulation and an f32 residual stream
 # (BASELINE config 5): towers with 128 or 256 filters, and at 9x9 with 128 filters attention layers too (the shipped MainNetwork;
 # each attention block one fused kernel, k_attention_h: fp16 projection input and weights, everything behind it f32).  "f16r" takes
-# attention-free towers only; "f32x3" also takes attention layers at 9x9 (one fused kernel each at 128 filters).  Anything else is
-# refused by tg_net_load.
+# attention-free towers only; "f32x3" also takes attention layers at 9x9 (one fused kernel each at 128 filters).  "f32" takes attention
+# layers at 9x9 and, with 128 or 256 filters, at 19x19 (the tiled k_attention_t); "f16" and "f32x3" with attention at 19x19 are still
+# refused.  Anything else is refused by tg_net_load.
 PRECISIONS = {"f32": 0, "f16": 1, "f16r": 2, "f32x3": 3}     # f16r: fp16 residual stream as well; f32x3: split precision (both opt-in)
 
 
