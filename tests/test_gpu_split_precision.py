@@ -51,8 +51,9 @@ def test_split_precision_tower_within_1e5_of_torch_f32(S, F, NB, n):
 @pytest.mark.parametrize("F,n", [(128, 300), (256, 40)])
 def test_split_precision_mainnetwork_with_attention(F, n):
     """The reference's shipped MainNetwork ("RARRRARRRRAR+P", model.py:49-76) under net_precision 3: its nine residual blocks on
-    the split-precision convs, the Self_Attention layers (trunk and policy head) on the f32 kernels, which hand a residual
-    block that follows its input already split (k_attention_mfma<..., X2O>).  Against the torch restatement that
+    the split-precision convs; the Self_Attention layers (trunk and policy head) at F = 128 on the fused k_attention_x3 (q/k/v
+    projected in split precision inside the block), at F = 256 on the f32 kernels (k_attention_mfma<..., X2O>) -- either hands a
+    residual block that follows its input already split.  Against the torch restatement that
     tests/golden/net_transgo_f32.npz pins, and against the exact-f32 HIP path on the same input."""
     import torch
     from oracle.net import TransGoMain
@@ -99,6 +100,35 @@ def test_split_precision_mainnetwork_with_attention(F, n):
         print(f"f32x3 MainNetwork F={F}, {nb} boards: max abs difference to the exact-f32 HIP path {eb[0]:.2e} {eb[1]:.2e} {eb[2]:.2e}")
         assert max(eb) < TOL
         assert np.array_equal(bp[:n], hp) and np.array_equal(bv[:n], hv) and np.array_equal(bo[:n], ho)
+
+
+@pytest.mark.parametrize("code", ["A", "AR", "AA", "RA+P"])
+def test_split_precision_short_archs(code):
+    """The fused k_attention_x3 in the smallest archs at which each of its paths can be wrong (9x9, F = 128), as
+    tests/test_gpu_half_attention.py has them for k_attention_h: "A" (attention after the stem; its split output carries the tail BN
+    for the head conv), "AR" (split output with the next block's bn1), "AA" (no split output between the two), "RA+P" (PRO).
+    Batches of 1, 7 and 1031 boards (more than 256 workgroups x 4 waves: some waves walk two boards, some one) within TOL of the
+    exact-f32 HIP path on the same batch; a board's result does not depend on its batch; nothing beyond fp16's range."""
+    from tests.half_attention_ref import arch_of, seeded_arch, state_dict_np
+    from transgo_amd.model import HipNetwork
+    big = 1031
+    sd = state_dict_np(seeded_arch(code, 9, 10, 128, 61))
+    x = _positions(9, big, 17)
+    h = HipNetwork(9, 10, 128, rows_cap=big, arch=arch_of(code), precision="f32x3")
+    h32 = HipNetwork(9, 10, 128, rows_cap=big, arch=arch_of(code))
+    try:
+        h.set_weights(sd); h32.set_weights(sd)
+        outs = {}
+        for n in (1, 7, big):
+            outs[n] = h.main_prediction(x[:n])
+            e = [float(np.abs(a - b).max()) for a, b in zip(outs[n], h32.main_prediction(x[:n]))]
+            print(f"\nf32x3 {code} n={n}: max abs difference to the exact-f32 HIP path policy {e[0]:.2e} value {e[1]:.2e} own {e[2]:.2e}")
+            assert max(e) < TOL, (code, n)
+        for a, b, c in zip(outs[1], outs[7], outs[big]):
+            assert np.array_equal(a, b[:1]) and np.array_equal(b, c[:7]), f"{code}: a board's result depends on its batch"
+        assert h.net_range()["fp16_overflows"] == 0
+    finally:
+        h.ctx.close(); h32.ctx.close()
 
 
 def test_split_precision_background_refresh_and_refusals():

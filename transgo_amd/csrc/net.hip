@@ -1754,387 +1754,60 @@ __global__ __launch_bounds__(256, 1) void k_attention_t(const float* __restrict_
     }
 }
 
-// Self_Attention as ONE kernel for the split-precision chain (net_precision 3, F = 128, 9x9): the q/k/v 1x1 projection is computed
-// inside the per-board core, on the fp16 matrix cores in split precision, and never goes through memory (the two-kernel form
-// moves 62 KB of q|k|v per board out and back in: at 16 k boards the pair took 0.61 + 0.70 ms, 23 % of a MainNetwork wave).
-//   * the split weights of the layer ([F/16 groups][W couts][hi 16 | lo 16], 64-B rows XOR-swizzled like the conv's stage tiles,
-//     scaled by 2^s; k_restage_att_split) sit in LDS for the life of a persistent workgroup (96 KB, one workgroup of 4 waves per CU);
-//   * one wave per board, as in k_attention_mfma.  x fragments are built from the f32 residual stream on the fly: lane (j, kq) loads
-//     8 channels of row j and keeps their fp16 hi (kq < 2) or lo (kq >= 2) halves -- the [a_hi | a_lo] operand of a K = 32 step;
+// Self_Attention as ONE kernel (F = 128, 9x9), one body (att_fused_block.h, included below once per precision and again behind
+// k_restage_att_split) for two precisions of the q/k/v 1x1 projection: the projection is computed
+// inside the per-board core on the fp16 matrix cores and never goes through memory (the two-kernel form moves 62 KB of q|k|v per
+// board out and back in: at 16 k boards the pair took 0.61 + 0.70 ms, 23 % of a MainNetwork wave).
+//   SPLIT   (k_attention_x3, net_precision 3) split precision: x and the weights as fp16 hi + lo, three of the four products;
+//   !SPLIT  (k_attention_h, net_precision 1)  a single fp16 product: what rounds to fp16 is the projection's input (x, under PRO
+//           relu(x*ps + pt)) and its weights.
+// The biases, q, k, v, the energy GEMM, the softmax, the output GEMM, gamma, the residual and the block's BN are f32 in both.
+//   * the layer's weights sit in LDS for the life of a persistent workgroup (one workgroup of 4 waves per CU), [NG groups][W couts]
+//     [32 halfs], the 64-B rows XOR-swizzled like the conv's stage tiles; one K = 32 step of v_mfma_f32_16x16x32_f16 covers a group.
+//     SPLIT: groups of 16 channels as [hi 16 | lo 16], scaled by 2^s (k_restage_att_split), 96 KB.  !SPLIT: groups of 32 channels
+//     of plain fp16 (k_restage_att_half; no scale), 48 KB -- two images (57 KB each with parameters and touch scratch) would fit
+//     the LDS, but the output accumulators (192 registers) and q^T / k^T (96) alone are more than the 256 registers a second wave
+//     per SIMD would leave;
+//   * one wave per board, as in k_attention_mfma.  x fragments are built from the f32 residual stream on the fly, from two 16-B loads
+//     per lane (j, kq) of row j.  SPLIT: 8 adjacent channels of the group, of which the lane keeps the fp16 hi (kq < 2) or lo
+//     (kq >= 2) halves -- the [a_hi | a_lo] operand of a K = 32 step.  !SPLIT: channels g*32 + kq*4 .. +3 and g*32 + 16 + kq*4 .. +3,
+//     rounded once; the lane's K slots kq*8 + e hold those eight in that order and the image's rows are stored in the same order.
+//     With that order the lane's two loads ARE its elements of the two D tiles ct = 2g, 2g + 1 of column j (row = channel
+//     ct*16 + kq*4 + r): the residual goes from the row registers into the output accumulators with no shuffle (SPLIT needs 32
+//     ds_bpermute per row block);
 //   * phase A: q^T and k^T for the whole board, as D[c][pos] tiles -- which ARE the A / B operand layouts of the energy GEMM's f32
-//     16x16x4 steps (k index = 4*(lane >> 4) + r).  A three-stage stream over the 16-channel groups: group g on the matrix cores,
-//     group g+1 being split (VALU work in the shadow of the MFMAs), group g+2's loads in flight;
+//     16x16x4 steps (k index = 4*(lane >> 4) + r).  A three-stage stream over the channel groups: group g on the matrix cores,
+//     group g+1 being converted (VALU work in the shadow of the MFMAs), group g+2's loads in flight.  The f32 biases start the
+//     accumulators (SPLIT: added behind the GEMM, with the weight scale);
 //   * phase B, per block of 16 rows i (tm): v for those rows and all channels as D[pos][c] tiles -- the A operand layout of the
 //     output GEMM -- from the block's x rows (second pass over x; measured, it comes from HBM again: a board's 41 KB do not survive
 //     in an L2 shared by 128 boards in flight); the block's 16 x 96 energies; softmax on the accumulator tiles with DPP row
 //     reductions (a row is complete within the block); out[c][j] += (gamma v)[i][c] attention[i][j] into accumulators that cover all
 //     channels and also take the residual x of column tile tm in block tm (from the lines the block's row loads just fetched).
 //     Nothing but those accumulators outlives a block, so the 36 energy tiles of k_attention_mfma never exist at once and x is
-//     split twice per board, not once per channel pass.
-//   * epilogue: y = relu(bn(acc)) row-major and the next residual block's split input -- stores only (a load in here would queue
-//     behind the stores: vmcnt is in order); the next board's first two groups are requested before the first store, its lines
-//     were touched towards L2 (LDS-DMA into a scratch KB) at the start of phase B.
-// Per board: 1152 K=32 fp16 steps (projection) + 1296 f32 16x16x4 steps (exact-f32 energy and output GEMMs) = 59 k cycles of MFMA;
-// measured 130 k cycles per board (0.98 ms per 16 k boards; MFMA pipe 40 % busy).  PRO: x is relu(x*ps + pt) first (attention in
-// the policy head, model.py:94,106).  Diagnostics: -DTG_ATT_STAMP (phase stamps, scripts/stamp_att.py).
-// NM MFMAs with KV VALU instructions (the split of the next group) in the shadow of each
+//     converted twice per board, not once per channel pass.
+//   * epilogue: y = relu(bn(acc)) row-major and the next residual block's fp16 input (SPLIT: hi and lo planes, x2_index; !SPLIT: one
+//     plane, h16_index) -- stores only (a load in here would queue behind the stores: vmcnt is in order); the next board's first two
+//     groups are requested before the first store, its lines were touched towards L2 (LDS-DMA into a scratch KB) at the start of
+//     phase B.
+// Per board, SPLIT: 1152 K=32 fp16 steps (projection) + 1296 f32 16x16x4 steps (exact-f32 energy and output GEMMs) = 59 k cycles of
+// MFMA; measured 130 k cycles per board (0.98 ms per 16 k boards; MFMA pipe 40 % busy).  !SPLIT: 288 K=32 steps (96 for q^T / k^T,
+// 6 x 32 for v) + the same 1296.  PRO: x is relu(x*ps + pt) first (attention in the policy head, model.py:94,106).
+// Diagnostics: -DTG_ATT_STAMP (phase stamps of the SPLIT kernel, scripts/stamp_att.py).
+// NM MFMAs with KV VALU instructions (the conversion of the next group) in the shadow of each
 #define TG_ATT_SCHED(NM, KV) do { _Pragma("unroll") for (int i_ = 0; i_ < (NM); ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); \
                                   __builtin_amdgcn_sched_group_barrier(0x002, (KV), 0); } __builtin_amdgcn_sched_barrier(0); } while (0)
 #ifdef TG_ATT_STAMP
-// diagnostic build: phase stamps (s_memtime, 100 MHz) of the third board of wave 0 of workgroup 0, PRO = false launches
+// diagnostic build: phase stamps (s_memtime, 100 MHz) of the third board of wave 0 of workgroup 0, SPLIT, PRO = false launches
 __device__ unsigned long long g_att_stamp[32];
-#define TG_ASTAMP(i) do { __builtin_amdgcn_sched_barrier(0); if (!PRO && blockIdx.x == 0 && wave == 0 && nboard == 2 && lane == 0) g_att_stamp[i] = __builtin_readcyclecounter(); \
-                          __builtin_amdgcn_sched_barrier(0); } while (0)
+#define TG_ASTAMP(i) do { if constexpr (SPLIT) { __builtin_amdgcn_sched_barrier(0); if (!PRO && blockIdx.x == 0 && wave == 0 && nboard == 2 && lane == 0) g_att_stamp[i] = __builtin_readcyclecounter(); \
+                          __builtin_amdgcn_sched_barrier(0); } } while (0)
 #else
 #define TG_ASTAMP(i) do { } while (0)
 #endif
-template <int S, int F, bool PRO>
-__global__ __launch_bounds__(256, 1) void k_attention_x3(const float* __restrict__ xin, float* __restrict__ out, _Float16* __restrict__ out2,
-                                                         const _Float16* __restrict__ wimg, const float* __restrict__ qb,
-                                                         const float* __restrict__ wsc_p, const float* __restrict__ gamma,
-                                                         const float* __restrict__ bs, const float* __restrict__ bt,
-                                                         const float* __restrict__ ps, const float* __restrict__ pt,
-                                                         const float* __restrict__ s2, const float* __restrict__ t2, int rows,
-                                                         unsigned* __restrict__ ovf) {
-    constexpr int P = S * S, FQ = F / 4, W = 2 * FQ + F, NT = (P + 15) / 16, CT = F / 16, NG = F / 16, NSUB = FQ / 16;
-    static_assert(P <= 96 && FQ % 16 == 0 && NG % 2 == 0, "attention tile geometry");
-    extern __shared__ __attribute__((aligned(16))) unsigned char att_smem[];
-    _Float16* const wl = reinterpret_cast<_Float16*>(att_smem);                       // [NG][W][32]
-    for (int i = threadIdx.x; i < NG * W * 4; i += 256) reinterpret_cast<f32x4*>(wl)[i] = reinterpret_cast<const f32x4*>(wimg)[i];
-    // per-channel parameters behind the image: q|k|v bias [W], then bn scale / shift, next block's bn1 scale / shift, prologue scale /
-    // shift [F each].  Read from LDS, they neither pin registers across the board loop nor queue behind the epilogue's stores (vector
-    // memory loads and stores share the in-order vmcnt)
-    float* const prm = reinterpret_cast<float*>(att_smem + (size_t)NG * W * 64);
-    for (int i = threadIdx.x; i < W; i += 256) prm[i] = qb[i];
-    for (int i = threadIdx.x; i < F; i += 256) {
-        prm[W + i] = bs[i]; prm[W + F + i] = bt[i];
-        prm[W + 2 * F + i] = out2 ? s2[i] : 1.f; prm[W + 3 * F + i] = out2 ? t2[i] : 0.f;
-        prm[W + 4 * F + i] = PRO ? ps[i] : 1.f; prm[W + 5 * F + i] = PRO ? pt[i] : 0.f;
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // scalar: board pointers stay in SGPRs
-    const int j = lane & 15, kq = lane >> 4;
-    const float lo_neg = kq >> 1 ? -1.f : -0.f;                                      // -1: this lane carries the lo halves of x
-    const unsigned chx = (kq & 1) * 8;
-    const int whi = j * 32 + (((kq & 1) ^ swz64(j)) << 3), wlo = j * 32 + (((2 + (kq & 1)) ^ swz64(j)) << 3);
-    // ds_read offsets are 16-bit: the image's upper half gets its own (opaque) base so that no address needs a register of its own
-    int upper = NG / 2 * W * 32;
-    asm volatile("" : "+v"(upper));
-    const _Float16* const wl1 = wl + upper;
-    auto wgroup = [&](int g) { return g < NG / 2 ? wl + g * W * 32 : wl1 + (g - NG / 2) * W * 32; };
-    const float wsc = wsc_p[0];
-    const int M = rows * P;
-    // Addresses: tile t of a board starts 16 rows = 16*F floats further (a scalar add on the board pointer); within the tile lane j
-    // takes row j -- except in the last tile, where rows past the board clamp to its last row.  Three per-lane byte offsets serve
-    // every access: {first five tiles, last tile} x the 8-channel column of the projection reads, and the 4-channel column of the D tiles.
-    constexpr int LASTR = P - 1 - (NT - 1) * 16;                                     // last valid row of the last tile
-    const unsigned rowA = (unsigned)j * F * 4u, rowB = (unsigned)(j <= LASTR ? j : LASTR) * F * 4u;
-    const unsigned xoA = rowA + chx * 4u, xoB = rowB + chx * 4u, eoA = rowA + kq * 16u;
-    const unsigned hoA = ((unsigned)(kq >> 1) * M + j) * 16u + (kq & 1) * 8u;        // split chunk-major output, + t*256 per tile
-    auto tile = [](const float* board, int t) { return board + t * 16 * F; };
-    auto ld16 = [](const float* base, unsigned byte_off) { return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + byte_off); };
-    // 8 channels of one row -> this lane's half of the split fragment
-    const float* l_ps = nullptr; const float* l_pt = nullptr;                          // set per board (LDS parameter block)
-    struct Pro { f32x4 sc[2], sh[2]; };                                               // prologue scale / shift of this lane's 8 channels of a group
-    auto pro_of = [&](int g) {
-        Pro p{};
-        if constexpr (PRO) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) { p.sc[h] = *reinterpret_cast<const f32x4*>(l_ps + g * 16 + chx + 4 * h); p.sh[h] = *reinterpret_cast<const f32x4*>(l_pt + g * 16 + chx + 4 * h); }
-        }
-        return p;
-    };
-    // range guard (see conv_epilogue_h8): the largest |x| this wave split in phase A (phase B splits the same values again) and the
-    // largest value the epilogue rounds to fp16; checked once per board
-    float amax = 0.f;
-    auto split8 = [&](const f32x4 (&src)[2], const Pro& pr, bool track = false) -> h8 {
-        h8 xf;
-#pragma unroll
-        for (int e = 0; e < 8; e += 2) {
-            f32x2 v = {src[e >> 2][e & 3], src[e >> 2][(e & 3) + 1]};
-            if constexpr (PRO) {
-#pragma unroll
-                for (int q = 0; q < 2; ++q) { const float w = v[q] * pr.sc[e >> 2][(e & 3) + q] + pr.sh[e >> 2][(e & 3) + q]; v[q] = w > 0.f ? w : 0.f; }
-            }
-            if (track) amax = __builtin_fmaxf(amax, __builtin_fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])));
-            const f32x2 hi = __builtin_convertvector(__builtin_convertvector(v, h2), f32x2);
-            // hi lanes (lo_neg = -0): half(v); lo lanes (lo_neg = -1): half(v - hi), the product is exact either way
-            const f32x2 d = {__builtin_fmaf(lo_neg, hi[0], v[0]), __builtin_fmaf(lo_neg, hi[1], v[1])};
-            const h2 o = __builtin_convertvector(d, h2);
-            xf[e] = o[0]; xf[e + 1] = o[1];
-        }
-        return xf;
-    };
-    f32x4 rawA[NT][2], rawB[NT][2];                                                  // phase A stream: one group of all six tiles each
-    h8 xfA[NT], xfB[NT];
-    // (the lane offsets are made opaque where they are used: hoisted out of the board loop in their 64-bit form they are spilled, and the
-    // loads then take full VGPR addresses reloaded from scratch -- behind whatever the wave has in flight)
-    auto issue = [&](const float* xb, int g, f32x4 (&dst)[NT][2]) {
-        unsigned oa = xoA, ob = xoB;
-        asm volatile("" : "+v"(oa), "+v"(ob));
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            dst[t][0] = ld16(tile(xb, t), (t + 1 < NT ? oa : ob) + g * 64);
-            dst[t][1] = ld16(tile(xb, t), (t + 1 < NT ? oa : ob) + g * 64 + 16);
-        }
-    };
-    auto split = [&](const f32x4 (&src)[NT][2], int g, h8 (&xf)[NT]) {
-        const Pro pr = pro_of(g);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) xf[t] = split8(src[t], pr, true);
-    };
-    int b = blockIdx.x * 4 + wave;
-    if (b >= rows) return;
-    { const float* xb0 = xin + (size_t)b * P * F; issue(xb0, 0, rawB); issue(xb0, 1, rawA); }
-    int nboard = 0;
-    for (; b < rows; b += gridDim.x * 4, ++nboard) {
-        const float* xb = xin + (size_t)b * P * F;
-        // opaque per board: LDS is read-only from here on, so every parameter read would otherwise be hoisted out of the board loop
-        // (and pin, then spill, ~150 registers)
-        unsigned popq = 0;
-        asm volatile("" : "+v"(popq));                                                // (an opaque OFFSET: the pointer keeps its LDS address space)
-        const float* const l_qb = prm + popq;
-        const float* const l_bs = l_qb + W; const float* const l_bt = l_bs + F;
-        const float* const l_s2 = l_bt + F; const float* const l_t2 = l_s2 + F; l_ps = l_t2 + F; l_pt = l_ps + F;
-        TG_ASTAMP(0);
-        // ---- phase A: q^T and k^T, [c][pos] tiles ----
-        f32x4 qk[2 * NSUB][NT];
-#pragma unroll
-        for (int ct = 0; ct < 2 * NSUB; ++ct)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) qk[ct][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-        auto mfma_qk = [&](int g, const h8 (&xf)[NT]) {
-#pragma unroll
-            for (int ct = 0; ct < 2 * NSUB; ++ct) {
-                const _Float16* wr = wgroup(g) + ct * 16 * 32;
-                const h8 ah = *reinterpret_cast<const h8*>(wr + whi), al = *reinterpret_cast<const h8*>(wr + wlo);
-#pragma unroll
-                for (int t = 0; t < NT; ++t) qk[ct][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, xf[t], qk[ct][t], 0, 0, 0);
-#pragma unroll
-                for (int t = 0; t < NT; ++t) qk[ct][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, xf[t], qk[ct][t], 0, 0, 0);
-            }
-        };
-        split(rawB, 0, xfA);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int g = 0; g < NG; g += 2) {
-            if (g + 2 < NG) issue(xb, g + 2, rawB);
-            mfma_qk(g, xfA);
-            split(rawA, g + 1, xfB);
-            TG_ATT_SCHED(2 * NSUB * NT * 2, 3);
-            if (g + 3 < NG) issue(xb, g + 3, rawA);
-            mfma_qk(g + 1, xfB);
-            if (g + 2 < NG) split(rawB, g + 2, xfA);
-            TG_ATT_SCHED(2 * NSUB * NT * 2, 3);
-            if (g == 0) TG_ASTAMP(29);
-        }
-        TG_ASTAMP(1);
-        // ---- phase B, block tm = rows i in [16 tm, 16 tm + 16) ----
-        f32x4 rv[NG][2];                                                             // the block's x rows, all groups
-        auto issue_rows = [&](int tm) {
-            unsigned o = tm + 1 < NT ? xoA : xoB;
-            asm volatile("" : "+v"(o));
-#pragma unroll
-            for (int g = 0; g < NG; ++g) {
-                rv[g][0] = ld16(tile(xb, tm), o + g * 64);
-                rv[g][1] = ld16(tile(xb, tm), o + g * 64 + 16);
-            }
-        };
-        issue_rows(0);
-#pragma unroll
-        for (int ct = 0; ct < 2 * NSUB; ++ct) {
-            const f32x4 bq = *reinterpret_cast<const f32x4*>(l_qb + ct * 16 + kq * 4);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) qk[ct][t] = qk[ct][t] * wsc + bq;
-        }
-        // The residual x (PRO: relu(x*ps + pt)) is ADDED INTO the output accumulators, column tile tn in row block tm = tn, and v
-        // carries the factor gamma, so that they end as gamma * out + x and the epilogue has no loads at all: a load queued behind
-        // the epilogue's stores would wait for their acknowledgements (vmcnt is in order), and did -- 30 % of a board's time in the
-        // first version.  Taken in block tn, the residual rows are the lines that block's own row loads have just brought in (read
-        // up front for all tiles they were a third trip to HBM: 2.17 GB of reads per launch against 0.67 GB of x).
-        const float gam = gamma[0];
-        f32x4 acc[CT][NT];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int tn = 0; tn < NT; ++tn) acc[ct][tn] = f32x4{0.f, 0.f, 0.f, 0.f};
-        // next board's rows towards L2 now (one dword per 128-B line, results unused): phase A is the first touch of a board's x and
-        // its loads run only one group ahead of their use -- from HBM that was 17 % of a board's time
-        const int bnx = b + gridDim.x * 4;
-        const float* const xnext = xin + (size_t)(bnx < rows ? bnx : b) * P * F;
-        // as LDS-DMA into a scratch KB of this wave: no destination registers, nothing ever waits for them
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const unsigned lo = (unsigned)(lane + 64 * i) * 128u, off = lo < (unsigned)(P * F * 4 - 16) ? lo : (unsigned)(P * F * 4 - 16);
-            tg_dma_global(xnext, (int)off, (tg_lds_void*)(&att_smem[(size_t)NG * W * 64 + (W + 6 * F) * 4 + wave * 1024]));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        TG_ASTAMP(27);
-#pragma unroll
-        for (int tm = 0; tm < NT; ++tm) {
-            // v for the block: D[pos][c], all channel tiles
-            f32x4 va[CT];
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) va[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-            // weight fragments: eight in flight, each slot refilled (for the next half-group) right behind the MFMA that used it; the
-            // fences and group barriers keep that distance (left alone, the scheduler sinks every read next to its MFMA and the wave
-            // sits on LDS latency 128 times per block)
-            h8 wf[CT];
-            auto wslot = [&](int hg, int ct) {                                       // half-group hg = 2*g + (0: hi, 1: lo)
-                return *reinterpret_cast<const h8*>(wgroup(hg >> 1) + (2 * FQ + ct * 16) * 32 + ((hg & 1) ? wlo : whi));
-            };
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) wf[ct] = wslot(0, ct);
-            h8 xf = split8(rv[0], pro_of(0)), xfn = xf;
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int hg = 0; hg < 2 * NG; ++hg) {
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) {
-                    va[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf, wf[ct], va[ct], 0, 0, 0);
-                    if (hg + 1 < 2 * NG) wf[ct] = wslot(hg + 1, ct);
-                }
-                if ((hg & 1) == 0 && hg + 2 < 2 * NG) xfn = split8(rv[hg / 2 + 1], pro_of(hg / 2 + 1));   // next group's fragment, in the MFMA shadow
-#pragma unroll
-                for (int i_ = 0; i_ < CT; ++i_) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if (hg & 1) xf = xfn;
-            }
-            TG_ASTAMP(2 + 4 * tm);
-            __builtin_amdgcn_sched_barrier(0);
-            // the residual rows of column tile tm, D layout (row = channel ct*16 + kq*4 + r, column = position tm*16 + j).
-            // Taken from the block's ROW registers, which hold exactly these values in the
-            // projection layout -- lane (j, kq') has channels g*16 + (kq' & 1)*8 .. +7 of row j, the lane pairs kq' and kq' + 2
-            // hold the same eight -- so lanes kq' < 2 offer their first four, lanes kq' >= 2 their last four, and destination
-            // (j, kq) pulls from (j, (kq >> 1) + 2*(kq & 1)): one ds_bpermute per register, no memory access at all.  (Round 3
-            // read them from memory again: meant to be cache hits on the lines the row loads had just fetched, they were the third
-            // trip to HBM -- the XCD's L2 turns over within a row block, profiles/r3_pmc_attention_x3.json: 2.19 GB fetched.)
-            f32x4 xa[CT];
-            {
-                const int src = ((((kq >> 1) + 2 * (kq & 1)) << 4) + j) << 2;          // byte address of the source lane
-                const bool hi_half = kq >= 2;
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) {
-                    // (scalar copies: a bit_cast of a vector ELEMENT sends the whole vector through scratch)
-                    const float s0 = hi_half ? rv[ct][1][0] : rv[ct][0][0], s1 = hi_half ? rv[ct][1][1] : rv[ct][0][1];
-                    const float s2 = hi_half ? rv[ct][1][2] : rv[ct][0][2], s3 = hi_half ? rv[ct][1][3] : rv[ct][0][3];
-                    xa[ct] = f32x4{__int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(s0))), __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(s1))),
-                                   __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(s2))), __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(s3)))};
-                }
-            }
-            if (tm + 1 < NT) issue_rows(tm + 1);                                      // lands during the block's energy / output GEMMs
-            __builtin_amdgcn_sched_barrier(0);                                       // (kept here: sunk to the block's end they are waited for at once)
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) va[ct] = (va[ct] * wsc + l_qb[2 * FQ + ct * 16 + j]) * gam;
-            // energies of the block (exact f32): e[tn] = q[tm] . k[tn]
-            f32x4 e[NT];
-#pragma unroll
-            for (int tn = 0; tn < NT; ++tn) e[tn] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int sub = 0; sub < NSUB; ++sub)
-#pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-                    for (int tn = 0; tn < NT; ++tn)
-                        e[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(qk[sub][tm][s4], qk[NSUB + sub][tn][s4], e[tn], 0, 0, 0);
-            TG_ASTAMP(3 + 4 * tm);
-            // softmax over j (columns) for the rows i = tm*16 + kq*4 + r
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float mx = -INFINITY;
-#pragma unroll
-                for (int tn = 0; tn < NT; ++tn) if (tn * 16 + j < P) mx = e[tn][r] > mx ? e[tn][r] : mx;
-#pragma unroll
-                for (int o = 0; o < 4; ++o) { const float t = row16_step(mx, o); mx = t > mx ? t : mx; }
-                float sum = 0.f;
-#pragma unroll
-                for (int tn = 0; tn < NT; ++tn) {
-                    const float v = tn * 16 + j < P ? __expf(e[tn][r] - mx) : 0.f;        // v_exp_f32: ~1e-7 relative, tolerance is 1e-3
-                    e[tn][r] = v; sum += v;
-                }
-#pragma unroll
-                for (int o = 0; o < 4; ++o) sum += row16_step(sum, o);
-                const float inv = (tm * 16 + kq * 4 + r < P) ? 1.f / sum : 0.f;     // rows past the board contribute nothing below
-#pragma unroll
-                for (int tn = 0; tn < NT; ++tn) e[tn][r] *= inv;
-            }
-            TG_ASTAMP(4 + 4 * tm);
-            // out[c][j] += v[i][c] attention[i][j]: k-step r covers rows i = tm*16 + kq*4 + r; of the last block only the steps that
-            // touch a row < P exist
-            constexpr int LASTS = P - (NT - 1) * 16, NS_LAST = LASTS < 4 ? LASTS : 4;
-            const int ns = tm + 1 < NT ? 4 : NS_LAST;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (r >= ns) continue;
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                    for (int tn = 0; tn < NT; ++tn)
-                        acc[ct][tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[ct][r], e[tn][r], acc[ct][tn], 0, 0, 0);
-            }
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-                f32x4 xv = xa[ct];
-                if constexpr (PRO) {
-                    const f32x4 vps = *reinterpret_cast<const f32x4*>(l_ps + ct * 16 + kq * 4), vpt = *reinterpret_cast<const f32x4*>(l_pt + ct * 16 + kq * 4);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { const float w = xv[q] * vps[q] + vpt[q]; xv[q] = w > 0.f ? w : 0.f; }
-                }
-                acc[ct][tm] = acc[ct][tm] + xv;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            TG_ASTAMP(5 + 4 * tm);
-        }
-        // ---- epilogue.  D tile: row = channel ct*16 + kq*4 + r, column = position tn*16 + j ----
-        // every address = a per-board scalar base + one of six per-lane byte offsets + a compile-time constant.  Loads are kept
-        // AHEAD of the stores in issue order (a load queued behind stores waits for their acknowledgements): the next board's first
-        // two groups go out before the first store, and the residual is already inside the accumulators.
-        {
-            issue(xnext, 0, rawB); issue(xnext, 1, rawA);                             // unconditional (last board: its own rows again)
-        }
-        char* const yb = reinterpret_cast<char*>(out + (size_t)b * P * F);
-        // opaque per board: hoisted out of the board loop, the 64-bit forms of these offsets would be spilled -- and a spill reload in
-        // here queues behind the stores
-        unsigned eoE = eoA, hoE = hoA;
-        asm volatile("" : "+v"(eoE), "+v"(hoE));
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-            const int c = ct * 16 + kq * 4;
-            const f32x4 vbs = *reinterpret_cast<const f32x4*>(l_bs + c), vbt = *reinterpret_cast<const f32x4*>(l_bt + c);
-            const f32x4 vs2 = *reinterpret_cast<const f32x4*>(l_s2 + c), vt2 = *reinterpret_cast<const f32x4*>(l_t2 + c);
-            // split output: element (m, x2_index(c)) of the chunk-major tensor = chunk plane ct*4 + (kq >> 1) (lo: + 2), row m, half (kq & 1)*4
-            char* const hb = reinterpret_cast<char*>(out2) + ((size_t)ct * 4 * M + (size_t)b * P) * 16;
-            char* const lb = hb + (size_t)2 * M * 16;
-#pragma unroll
-            for (int tn = 0; tn < NT; ++tn) {
-                if (tn * 16 + j >= P) continue;
-                f32x4 y, u;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float w = acc[ct][tn][q] * vbs[q] + vbt[q];
-                    y[q] = w > 0.f ? w : 0.f;
-                    const float z = y[q] * vs2[q] + vt2[q];
-                    u[q] = z > 0.f ? z : 0.f;
-                }
-                *reinterpret_cast<f32x4*>(yb + tn * 16 * F * 4 + (eoE + ct * 64)) = y;
-                if (out2) {
-                    h4 hi, lo;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { hi[q] = (_Float16)u[q]; lo[q] = (_Float16)(u[q] - (float)hi[q]); amax = __builtin_fmaxf(amax, u[q]); }
-                    *reinterpret_cast<h4*>(hb + (hoE + tn * 256)) = hi;
-                    *reinterpret_cast<h4*>(lb + (hoE + tn * 256)) = lo;
-                }
-            }
-            if (ct == 3) TG_ASTAMP(28);
-        }
-        TG_ASTAMP(26);
-        if (__builtin_amdgcn_ballot_w64(!(amax <= 65504.f)) != 0) { if (lane == 0) atomicAdd(ovf, 1u); amax = 0.f; }
-    }
-    TG_VMCNT(0);                                                                     // the last board's touches and stores
-}
+#define TG_ATT_SPLIT 1
+#include "att_fused_block.h"   // k_attention_x3<S, F, PRO>
+#undef TG_ATT_SPLIT
 
 // the LDS image of k_attention_x3: dst[g][cout][32] = [hi of channels g*16..+15 | lo of the same] of w[cout][F] * 2^s, the four
 // 16-B chunks of a row XOR-swizzled by swz64(cout) (the fragment reads of the kernel undo it); wsc_out = 2^-s
@@ -2155,302 +1828,9 @@ __global__ __launch_bounds__(256) void k_restage_att_split(const float* __restri
     }
 }
 
-// Self_Attention as ONE kernel for the fp16-storage chain (net_precision 1, F = 128, 9x9): k_attention_x3 with a single fp16 product
-// in the q/k/v projection.  What rounds to fp16 is the projection's input (x, under PRO relu(x*ps + pt)) and its weights; the biases,
-// q, k, v, the energy GEMM, the softmax, the output GEMM, gamma, the residual and the block's BN are f32 exactly as in
-// k_attention_x3, whose phases this kernel keeps.  What differs:
-//   * the weight image is [F/32 groups][W couts][32 halfs] of plain fp16 (k_restage_att_half; no scale), 48 KB, the 64-B rows
-//     XOR-swizzled by swz64(cout) as everywhere; one K = 32 step of v_mfma_f32_16x16x32_f16 covers 32 real channels;
-//   * lane (j, kq) loads channels g*32 + kq*4 .. +3 and g*32 + 16 + kq*4 .. +3 of row j (two 16-B loads) and rounds them once; its K
-//     slots kq*8 + e hold those eight in that order and the image's rows are stored in the same order.  With that order the lane's two
-//     loads ARE its elements of the two D tiles ct = 2g, 2g + 1 of column j (row = channel ct*16 + kq*4 + r): the residual goes from
-//     the row registers into the output accumulators with no shuffle (k_attention_x3 needs 32 ds_bpermute per row block);
-//   * the f32 biases start the projection accumulators.
-// Per board: 288 K=32 fp16 steps (96 for q^T / k^T, 6 x 32 for v) + 1296 f32 16x16x4 steps.  One workgroup of 4 waves per CU: the
-// output accumulators (192 registers) and q^T / k^T (96) alone are more than the 256 registers a second wave per SIMD would leave,
-// although two images (57 KB each with parameters and touch scratch) would fit the LDS.
-template <int S, int F, bool PRO>
-__global__ __launch_bounds__(256, 1) void k_attention_h(const float* __restrict__ xin, float* __restrict__ out, _Float16* __restrict__ out2,
-                                                        const _Float16* __restrict__ wimg, const float* __restrict__ qb,
-                                                        const float* __restrict__ gamma,
-                                                        const float* __restrict__ bs, const float* __restrict__ bt,
-                                                        const float* __restrict__ ps, const float* __restrict__ pt,
-                                                        const float* __restrict__ s2, const float* __restrict__ t2, int rows,
-                                                        unsigned* __restrict__ ovf) {
-    constexpr int P = S * S, FQ = F / 4, W = 2 * FQ + F, NT = (P + 15) / 16, CT = F / 16, NG = F / 32, NSUB = FQ / 16;
-    static_assert(P <= 96 && FQ % 16 == 0 && NG % 2 == 0 && NG * W * 64 + (W + 6 * F) * 4 + 4096 <= 65536, "attention tile geometry");
-    extern __shared__ __attribute__((aligned(16))) unsigned char att_smem[];
-    _Float16* const wl = reinterpret_cast<_Float16*>(att_smem);                       // [NG][W][32]
-    for (int i = threadIdx.x; i < NG * W * 4; i += 256) reinterpret_cast<f32x4*>(wl)[i] = reinterpret_cast<const f32x4*>(wimg)[i];
-    // per-channel parameters behind the image, as in k_attention_x3: q|k|v bias [W], bn scale / shift, next layer's bn scale / shift,
-    // prologue scale / shift [F each]
-    float* const prm = reinterpret_cast<float*>(att_smem + (size_t)NG * W * 64);
-    for (int i = threadIdx.x; i < W; i += 256) prm[i] = qb[i];
-    for (int i = threadIdx.x; i < F; i += 256) {
-        prm[W + i] = bs[i]; prm[W + F + i] = bt[i];
-        prm[W + 2 * F + i] = out2 ? s2[i] : 1.f; prm[W + 3 * F + i] = out2 ? t2[i] : 0.f;
-        prm[W + 4 * F + i] = PRO ? ps[i] : 1.f; prm[W + 5 * F + i] = PRO ? pt[i] : 0.f;
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // scalar: board pointers stay in SGPRs
-    const int j = lane & 15, kq = lane >> 4;
-    const int wfo = j * 32 + ((kq ^ swz64(j)) << 3);                                 // this lane's 16-B chunk of weight row j
-    auto wgroup = [&](int g) { return wl + g * W * 32; };                            // (the whole image is within a ds_read's 16-bit offset)
-    const int M = rows * P;
-    // Addresses: tile t of a board starts 16 rows = 16*F floats further (a scalar add on the board pointer); within the tile lane j
-    // takes row j -- except in the last tile, where rows past the board clamp to its last row.  Channel kq*4 of the row serves the
-    // projection reads (+ g*128 B, + 64 B) and the D tiles of the epilogue (+ ct*64 B) alike.
-    constexpr int LASTR = P - 1 - (NT - 1) * 16;                                     // last valid row of the last tile
-    const unsigned eoA = (unsigned)j * F * 4u + kq * 16u, eoB = (unsigned)(j <= LASTR ? j : LASTR) * F * 4u + kq * 16u;
-    const unsigned hoA = ((unsigned)(kq >> 1) * M + j) * 16u + (kq & 1) * 8u;        // chunk-major fp16 output (h16_index), + t*256 per tile
-    auto tile = [](const float* board, int t) { return board + t * 16 * F; };
-    auto ld16 = [](const float* base, unsigned byte_off) { return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(base) + byte_off); };
-    const float* l_ps = nullptr; const float* l_pt = nullptr;                          // set per board (LDS parameter block)
-    struct Pro { f32x4 sc[2], sh[2]; };                                               // prologue scale / shift of this lane's 8 channels of a group
-    auto pro_of = [&](int g) {
-        Pro p{};
-        if constexpr (PRO) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) { p.sc[h] = *reinterpret_cast<const f32x4*>(l_ps + g * 32 + h * 16 + kq * 4); p.sh[h] = *reinterpret_cast<const f32x4*>(l_pt + g * 32 + h * 16 + kq * 4); }
-        }
-        return p;
-    };
-    // range guard (see conv_epilogue_h8): the largest |x| this wave rounded in phase A (phase B rounds the same values again) and the
-    // largest value the epilogue rounds to fp16; checked once per board.  As in the conv epilogue, fmaxf drops a NaN operand: what is
-    // counted is a value beyond +-65504 (inf included), the event that first produces NaNs downstream -- a NaN that arrives is not
-    float amax = 0.f;
-    auto half8 = [&](const f32x4 (&src)[2], const Pro& pr, bool track = false) -> h8 {
-        h8 xf;
-#pragma unroll
-        for (int e = 0; e < 8; e += 2) {
-            f32x2 v = {src[e >> 2][e & 3], src[e >> 2][(e & 3) + 1]};
-            if constexpr (PRO) {
-#pragma unroll
-                for (int q = 0; q < 2; ++q) { const float w = v[q] * pr.sc[e >> 2][(e & 3) + q] + pr.sh[e >> 2][(e & 3) + q]; v[q] = w > 0.f ? w : 0.f; }
-            }
-            if (track) amax = __builtin_fmaxf(amax, __builtin_fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])));
-            const h2 o = __builtin_convertvector(v, h2);
-            xf[e] = o[0]; xf[e + 1] = o[1];
-        }
-        return xf;
-    };
-    f32x4 rawA[NT][2], rawB[NT][2];                                                  // phase A stream: one group of all six tiles each
-    h8 xfA[NT], xfB[NT];
-    // (the lane offsets are made opaque where they are used, as in k_attention_x3: hoisted in their 64-bit form they are spilled)
-    auto issue = [&](const float* xb, int g, f32x4 (&dst)[NT][2]) {
-        unsigned oa = eoA, ob = eoB;
-        asm volatile("" : "+v"(oa), "+v"(ob));
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            dst[t][0] = ld16(tile(xb, t), (t + 1 < NT ? oa : ob) + g * 128);
-            dst[t][1] = ld16(tile(xb, t), (t + 1 < NT ? oa : ob) + g * 128 + 64);
-        }
-    };
-    auto round_group = [&](const f32x4 (&src)[NT][2], int g, h8 (&xf)[NT]) {
-        const Pro pr = pro_of(g);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) xf[t] = half8(src[t], pr, true);
-    };
-    int b = blockIdx.x * 4 + wave;
-    if (b >= rows) return;
-    { const float* xb0 = xin + (size_t)b * P * F; issue(xb0, 0, rawB); issue(xb0, 1, rawA); }
-    for (; b < rows; b += gridDim.x * 4) {
-        const float* xb = xin + (size_t)b * P * F;
-        // opaque per board: LDS is read-only from here on, so every parameter read would otherwise be hoisted out of the board loop
-        unsigned popq = 0;
-        asm volatile("" : "+v"(popq));                                                // (an opaque OFFSET: the pointer keeps its LDS address space)
-        const float* const l_qb = prm + popq;
-        const float* const l_bs = l_qb + W; const float* const l_bt = l_bs + F;
-        const float* const l_s2 = l_bt + F; const float* const l_t2 = l_s2 + F; l_ps = l_t2 + F; l_pt = l_ps + F;
-        // ---- phase A: q^T and k^T, [c][pos] tiles, the f32 bias in the accumulator ----
-        f32x4 qk[2 * NSUB][NT];
-#pragma unroll
-        for (int ct = 0; ct < 2 * NSUB; ++ct) {
-            const f32x4 bq = *reinterpret_cast<const f32x4*>(l_qb + ct * 16 + kq * 4);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) qk[ct][t] = bq;
-        }
-        auto mfma_qk = [&](int g, const h8 (&xf)[NT]) {
-#pragma unroll
-            for (int ct = 0; ct < 2 * NSUB; ++ct) {
-                const h8 a = *reinterpret_cast<const h8*>(wgroup(g) + ct * 16 * 32 + wfo);
-#pragma unroll
-                for (int t = 0; t < NT; ++t) qk[ct][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, xf[t], qk[ct][t], 0, 0, 0);
-            }
-        };
-        round_group(rawB, 0, xfA);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int g = 0; g < NG; g += 2) {
-            if (g + 2 < NG) issue(xb, g + 2, rawB);
-            mfma_qk(g, xfA);
-            round_group(rawA, g + 1, xfB);
-            TG_ATT_SCHED(2 * NSUB * NT, 4);
-            if (g + 3 < NG) issue(xb, g + 3, rawA);
-            mfma_qk(g + 1, xfB);
-            if (g + 2 < NG) round_group(rawB, g + 2, xfA);
-            TG_ATT_SCHED(2 * NSUB * NT, 4);
-        }
-        // ---- phase B, block tm = rows i in [16 tm, 16 tm + 16) ----
-        f32x4 rv[NG][2];                                                             // the block's x rows, all groups
-        auto issue_rows = [&](int tm) {
-            unsigned o = tm + 1 < NT ? eoA : eoB;
-            asm volatile("" : "+v"(o));
-#pragma unroll
-            for (int g = 0; g < NG; ++g) {
-                rv[g][0] = ld16(tile(xb, tm), o + g * 128);
-                rv[g][1] = ld16(tile(xb, tm), o + g * 128 + 64);
-            }
-        };
-        issue_rows(0);
-        // The residual x (PRO: relu(x*ps + pt)) is ADDED INTO the output accumulators and v carries the factor gamma, so that they
-        // end as gamma * out + x and the epilogue has no loads at all (see k_attention_x3)
-        const float gam = gamma[0];
-        f32x4 acc[CT][NT];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int tn = 0; tn < NT; ++tn) acc[ct][tn] = f32x4{0.f, 0.f, 0.f, 0.f};
-        // next board's rows towards L2 now (one dword per 128-B line, as LDS-DMA into a scratch KB of this wave: results unused)
-        const int bnx = b + gridDim.x * 4;
-        const float* const xnext = xin + (size_t)(bnx < rows ? bnx : b) * P * F;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const unsigned lo = (unsigned)(lane + 64 * i) * 128u, off = lo < (unsigned)(P * F * 4 - 16) ? lo : (unsigned)(P * F * 4 - 16);
-            tg_dma_global(xnext, (int)off, (tg_lds_void*)(&att_smem[(size_t)NG * W * 64 + (W + 6 * F) * 4 + wave * 1024]));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int tm = 0; tm < NT; ++tm) {
-            // v for the block: D[pos][c], all channel tiles, the bias in the accumulator
-            f32x4 va[CT];
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) { const float bv = l_qb[2 * FQ + ct * 16 + j]; va[ct] = f32x4{bv, bv, bv, bv}; }
-            // weight fragments: eight in flight, each slot refilled (for the next group) right behind the MFMA that used it
-            h8 wf[CT];
-            auto wslot = [&](int g, int ct) { return *reinterpret_cast<const h8*>(wgroup(g) + (2 * FQ + ct * 16) * 32 + wfo); };
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) wf[ct] = wslot(0, ct);
-            h8 xf = half8(rv[0], pro_of(0)), xfn = xf;
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int g = 0; g < NG; ++g) {
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) {
-                    va[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf, wf[ct], va[ct], 0, 0, 0);
-                    if (g + 1 < NG) wf[ct] = wslot(g + 1, ct);
-                }
-                if (g + 1 < NG) xfn = half8(rv[g + 1], pro_of(g + 1));                  // next group's fragment, in the MFMA shadow
-#pragma unroll
-                for (int i_ = 0; i_ < CT; ++i_) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                xf = xfn;
-            }
-            // the residual rows of column tile tm: D tile ct = 2g + h (row = channel ct*16 + kq*4 + r, column = position tm*16 + j) is
-            // this lane's own rv[g][h] -- added now, before the next block's rows overwrite the registers
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-                f32x4 xv = rv[ct >> 1][ct & 1];
-                if constexpr (PRO) {
-                    const f32x4 vps = *reinterpret_cast<const f32x4*>(l_ps + ct * 16 + kq * 4), vpt = *reinterpret_cast<const f32x4*>(l_pt + ct * 16 + kq * 4);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { const float w = xv[q] * vps[q] + vpt[q]; xv[q] = w > 0.f ? w : 0.f; }
-                }
-                acc[ct][tm] = acc[ct][tm] + xv;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (tm + 1 < NT) issue_rows(tm + 1);                                      // lands during the block's energy / output GEMMs
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) va[ct] = va[ct] * gam;
-            // energies of the block (exact f32): e[tn] = q[tm] . k[tn]
-            f32x4 e[NT];
-#pragma unroll
-            for (int tn = 0; tn < NT; ++tn) e[tn] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int sub = 0; sub < NSUB; ++sub)
-#pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-                    for (int tn = 0; tn < NT; ++tn)
-                        e[tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(qk[sub][tm][s4], qk[NSUB + sub][tn][s4], e[tn], 0, 0, 0);
-            // softmax over j (columns) for the rows i = tm*16 + kq*4 + r
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float mx = -INFINITY;
-#pragma unroll
-                for (int tn = 0; tn < NT; ++tn) if (tn * 16 + j < P) mx = e[tn][r] > mx ? e[tn][r] : mx;
-#pragma unroll
-                for (int o = 0; o < 4; ++o) { const float t = row16_step(mx, o); mx = t > mx ? t : mx; }
-                float sum = 0.f;
-#pragma unroll
-                for (int tn = 0; tn < NT; ++tn) {
-                    const float v = tn * 16 + j < P ? __expf(e[tn][r] - mx) : 0.f;
-                    e[tn][r] = v; sum += v;
-                }
-#pragma unroll
-                for (int o = 0; o < 4; ++o) sum += row16_step(sum, o);
-                const float inv = (tm * 16 + kq * 4 + r < P) ? 1.f / sum : 0.f;     // rows past the board contribute nothing below
-#pragma unroll
-                for (int tn = 0; tn < NT; ++tn) e[tn][r] *= inv;
-            }
-            // out[c][j] += v[i][c] attention[i][j]: k-step r covers rows i = tm*16 + kq*4 + r; of the last block only the steps that
-            // touch a row < P exist
-            constexpr int LASTS = P - (NT - 1) * 16, NS_LAST = LASTS < 4 ? LASTS : 4;
-            const int ns = tm + 1 < NT ? 4 : NS_LAST;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (r >= ns) continue;
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                    for (int tn = 0; tn < NT; ++tn)
-                        acc[ct][tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(va[ct][r], e[tn][r], acc[ct][tn], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // ---- epilogue.  D tile: row = channel ct*16 + kq*4 + r, column = position tn*16 + j.  Stores only: the next board's first
-        // two groups go out before the first store, and the residual is already inside the accumulators ----
-        {
-            issue(xnext, 0, rawB); issue(xnext, 1, rawA);                             // unconditional (last board: its own rows again)
-        }
-        char* const yb = reinterpret_cast<char*>(out + (size_t)b * P * F);
-        unsigned eoE = eoA, hoE = hoA;
-        asm volatile("" : "+v"(eoE), "+v"(hoE));
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-            const int c = ct * 16 + kq * 4;
-            const f32x4 vbs = *reinterpret_cast<const f32x4*>(l_bs + c), vbt = *reinterpret_cast<const f32x4*>(l_bt + c);
-            const f32x4 vs2 = *reinterpret_cast<const f32x4*>(l_s2 + c), vt2 = *reinterpret_cast<const f32x4*>(l_t2 + c);
-            // fp16 output: element (m, c) of the chunk-major tensor = chunk plane c >> 3 = ct*2 + (kq >> 1), row m, half (kq & 1)*4
-            const size_t hplane = ((size_t)ct * 2 * M + (size_t)b * P) * 16;
-#pragma unroll
-            for (int tn = 0; tn < NT; ++tn) {
-                if (tn * 16 + j >= P) continue;
-                f32x4 y, u;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float w = acc[ct][tn][q] * vbs[q] + vbt[q];
-                    y[q] = w > 0.f ? w : 0.f;
-                    const float z = y[q] * vs2[q] + vt2[q];
-                    u[q] = z > 0.f ? z : 0.f;
-                }
-                *reinterpret_cast<f32x4*>(yb + tn * 16 * F * 4 + (eoE + ct * 64)) = y;
-                if (out2) {
-                    h4 o;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { o[q] = (_Float16)u[q]; amax = __builtin_fmaxf(amax, u[q]); }
-                    *reinterpret_cast<h4*>(reinterpret_cast<char*>(out2) + hplane + (hoE + tn * 256)) = o;
-                }
-            }
-        }
-        if (__builtin_amdgcn_ballot_w64(!(amax <= 65504.f)) != 0) { if (lane == 0) atomicAdd(ovf, 1u); amax = 0.f; }
-    }
-    TG_VMCNT(0);                                                                     // the last board's touches and stores
-}
+#define TG_ATT_SPLIT 0
+#include "att_fused_block.h"   // k_attention_h<S, F, PRO>
+#undef TG_ATT_SPLIT
 
 // the LDS image of k_attention_h: dst[g][cout][32] = half(w[cout][g*32 + ch(kk)]), kk the logical K slot of the physical position (the
 // four 16-B chunks of a row XOR-swizzled by swz64(cout)), ch(kk) = (kk >> 2 & 1)*16 + (kk >> 3)*4 + (kk & 3): lane kq's slots
@@ -2821,7 +2201,6 @@ void bind_weights(Net* n, int k) {
     n->layers.clear();
     const size_t per = 9 * (size_t)F * F;
     int ri = 0, ai = 0;
-    int n_att = pol ? 1 : 0; for (char c : trunk) n_att += c == 'A';
     // halfs per attention layer: k_attention_x3's LDS image (hi | lo per 16 channels), or k_attention_h's (plain fp16)
     const size_t att_img = (size_t)F / (n->path.att_h ? 32 : 16) * Wq * 32;
     auto bind_x3 = [&](AttW& a) { if (w.att_h) { a.x3w = w.att_h + (size_t)ai * att_img; if (w.att_sc) a.x3sc = w.att_sc + ai; } ++ai; };
@@ -2843,7 +2222,6 @@ void bind_weights(Net* n, int k) {
     }
     n->s_end = take(F); n->t_end = take(F);
     if (pol) { take_att(n->patt); bind_x3(n->patt); n->head_a.w = take(9 * 16 * (size_t)F); n->head_a.b = take(16); }
-    (void)n_att;
     n->head.w = take(9 * 16 * (size_t)F); n->head.b = take(16);
     n->w_vo = take(2 * P * 64); n->b_vo = take(64); n->w_v = take(64); n->b_v = take(1);
     n->w_o = take(64 * P); n->b_o = take(P); n->w_a = take(4 * P * A); n->b_a = take(A);
