@@ -41,15 +41,20 @@ for k in sorted(set(fe) | set(wr)):
     e = {"launches_summarised": len(f), "grid_size_median": grid, "FETCH_SIZE_KB_raw_median": round(fk, 1), "WRITE_SIZE_KB_median": round(wk, 1),
          "hbm_bytes_per_launch": round((2 * fk + wk) * 1024.0, 1), "duration_us_median": round(statistics.median(x[2] for x in f) / 1e3, 2)}
     if conv:
-        epi = int(k.split(",")[2].strip(" >"))                                                # k_conv3x3_sg<S, F, EPI>
+        targs = [t.strip(" >") for t in k.split(",")]                                         # k_conv3x3_sg<S, F, EPI[, SIN, SOUT]>
+        epi = int(targs[2])
         rows = grid / 256 * 128                        # one workgroup per (128 boards, position): workgroups * 128 = boards * P = rows
-        alg = (8 * F if epi == 0 else 16 * F) * rows
+        # EPI 1 reads h and the residual and writes the stream: 12F bytes per row; the two-tensor chain (no SIN / SOUT) also wrote
+        # the next block's activated input, 16F.  Told apart by the template arguments, which holds for what this script is run on:
+        # the default arm (or TG_ONE_STREAM=0) of a pure tower -- TG_ONE_STREAM=2 writes the copy from <.., true, true> too, and a
+        # block between attention layers or in front of the head writes none from <.., false, false>
+        alg = (8 * F if epi == 0 else 12 * F if "true" in targs[3:] else 16 * F) * rows
         e.update(boards_per_workgroup=128, rows_per_launch_approx=int(rows), algorithmic_bytes_per_launch=int(alg),
                  traffic_over_algorithmic=round(e["hbm_bytes_per_launch"] / alg, 3))
     out["kernels"][k] = e
 convs = [v for k, v in out["kernels"].items() if "k_conv3x3_sg" in k and v["launches_summarised"] > 50]
-out["dominant_kernel"] = ("k_conv3x3_sg<9,128,EPI> (EPI 0: relu; EPI 1: residual + next block's activated input; one workgroup per board "
-                          "position x 128 boards, off-board taps skipped)")
+out["dominant_kernel"] = ("k_conv3x3_sg<9,128,EPI,SIN,SOUT> (EPI 0: relu, SIN: input activated on load; EPI 1: residual stream in the conv's "
+                          "row order in (SIN) and out (SOUT); one workgroup per board position x 128 boards, off-board taps skipped)")
 out["hbm_bytes_per_launch_mean"] = sum(v["hbm_bytes_per_launch"] for v in convs) / len(convs)
 out["algorithmic_bytes_per_launch_mean"] = sum(v["algorithmic_bytes_per_launch"] for v in convs) / len(convs)
 tc, ta = out["kernels"]["k_collect<9>"], out["kernels"]["k_absorb<9>"]

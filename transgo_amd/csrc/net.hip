@@ -37,8 +37,13 @@ struct Layer { int kind; int ridx; AttW a; };                                   
 // Which forward runs, decided once at load (net_path) and read by the buffer allocation, the weight restaging and forward_t.
 //   CHAIN_F32   general f32 chain: k_conv3x3 everywhere (F = 32 / 64, TG_DMA_CONV=0, and the DMA
 //               chain's batches of 2 GiB or more per activation buffer)
-//   CHAIN_DMA   f32 tower of 128 / 256 filters on the DMA-fed k_conv3x3_sg; every producer also writes relu(bn1_next(.))
-//               slice-major for a residual block that follows, so the F->F kernels never activate anything
+//   CHAIN_DMA   f32 tower of 128 / 256 filters on the DMA-fed k_conv3x3_sg.  Between two conv layers (stem or residual block ->
+//               residual block) the residual stream is ONE f32 tensor, slice-major in the conv's row order (conv_rows.h): the producer
+//               writes nothing else, the block's first conv applies relu(bn1(.)) to its B fragments as they land, its second conv
+//               starts its accumulators from the stream.  Towards an attention layer or the head the stream is row-major, and an
+//               attention layer also writes relu(bn1_next(.)) slice-major (bufAct) for a residual block that follows it.
+//               TG_ONE_STREAM=0 (read at the load, like TG_DMA_CONV) selects the chain this replaced -- a row-major stream and
+//               bufAct behind every producer -- and 2 the single stream with bufAct still written and read (no activation on load)
 //   CHAIN_F16   fp16 storage, f32 accumulate (k_conv3x3_h2; stem and head conv too); the residual stream stays f32 unless r16
 //   CHAIN_SPLIT split precision ("f32x3"): every conv operand as fp16 hi + lo, three of the four products on the fp16 MFMA; the
 //               residual stream, the dense heads and (beyond the fused k_attention_x3) attention stay f32
@@ -50,6 +55,8 @@ struct NetPath {
     bool att_h = false;        // CHAIN_F16, f32 residual stream: attention blocks on the fused k_attention_h (9x9, F = 128)
     bool head_x2 = false;      // CHAIN_SPLIT: the head conv on k_head_gemm_x2 (F = 128, the trunk ends in a residual block)
     size_t att_lds = 0;        // k_attention's dynamic LDS in bytes; 0: no attention, or its image does not fit
+    int one_stream = 0;        // CHAIN_DMA: 1 between conv layers ONE f32 residual stream in the conv's row order, activated on load
+                               // (default); 2 that stream, relu(bn1_next(.)) still written beside it; 0 (TG_ONE_STREAM=0) two tensors
 };
 
 struct Net {
@@ -59,7 +66,7 @@ struct Net {
     ConvW stem; std::vector<BlockW> blocks; std::vector<Layer> layers; const float* s_end = nullptr; const float* t_end = nullptr;
     bool pol_att = false; AttW patt; ConvW head_a; std::string arch;
     float* bufQ = nullptr; float* hca = nullptr;   // q|k|v projections [rows][P][1.5F]; policy head conv output
-    float* bufAct = nullptr;                       // pre-activated input of the next conv (DMA path)
+    float* bufAct = nullptr;                       // DMA chain: relu(bn1(.)) for a residual block's first conv where its input is not activated on load
     int prec = 0;                                  // cfg.net_precision: 0 = f32, 1 = fp16 storage + f32 accumulate (k_conv3x3_h2), 2 = 1 + fp16 residual stream,
                                                    // 3 = split precision ("f32x3"): every operand as fp16 hi + lo, three of the four products on the fp16 MFMA, f32 accumulate
     const float* head_g = nullptr; const float* head_ag = nullptr;   // [64][F] head conv weights for k_head_gemm (tap*6 + cout rows)
@@ -148,6 +155,18 @@ __global__ __launch_bounds__(256) void k_bits_to_rows(const uint32_t* __restrict
 // contiguous KB.  The rows of the absent boards of the last group of 16 are never written (stale or uninitialised, NaN included):
 // they only ever feed MFMA columns of those same absent boards, which are never stored.
 __device__ __forceinline__ size_t f32_sm_index(int srow, int c, int Msm) { return ((size_t)(c >> 4) * Msm + srow) * 16 + (c & 15); }
+// relu(bn(v)) of a pre-activation residual block's input: the ONE expression behind `out2` and behind k_conv3x3_sg's activation on
+// load, so both give the same bits
+__device__ __forceinline__ float bn_relu(float v, float s, float t) { const float w = v * s + t; return w > 0.f ? w : 0.f; }
+// bn_relu beside MFMAs: the same two roundings (this library is built without contraction), spelled as single v_mul_f32 / v_add_f32
+// because the compiler SLP-packs neighbouring elements into v_pk_mul_f32 / v_pk_add_f32, which cost the MFMA pipe issue cycles
+// (MI355X_MICROARCH.md, constants table: packed f32 VALU beside MFMAs)
+__device__ __forceinline__ float bn_relu_unpacked(float v, float s, float t) {
+    float w;
+    asm("v_mul_f32 %0, %1, %2" : "=v"(w) : "v"(v), "v"(s));
+    asm("v_add_f32 %0, %1, %2" : "=v"(w) : "v"(w), "v"(t));
+    return w > 0.f ? w : 0.f;
+}
 
 template <int COUT, int CT, int NPT, int EPI, bool SM = false, bool SM2 = false>
 __device__ __forceinline__ void conv_epilogue(f32x4 (&acc)[CT][NPT], const int (&mrow)[NPT], int M, int co_base, int kq,
@@ -188,7 +207,7 @@ __device__ __forceinline__ void conv_epilogue(f32x4 (&acc)[CT][NPT], const int (
                     const f32x4 sh = *reinterpret_cast<const f32x4*>(par + 2 * COUT + col);
                     f32x4 u;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) { float w = v[e] * sc[e] + sh[e]; u[e] = w > 0.f ? w : 0.f; }
+                    for (int e = 0; e < 4; ++e) u[e] = bn_relu(v[e], sc[e], sh[e]);
                     *reinterpret_cast<f32x4*>(out2 + (SM2 ? f32_sm_index(srow[t], co_base + col, Msm) : (size_t)mrow[t] * COUT + co_base + col)) = u;
                 }
             }
@@ -198,7 +217,8 @@ __device__ __forceinline__ void conv_epilogue(f32x4 (&acc)[CT][NPT], const int (
 
 // EPI 0: out = relu(acc + bias)      EPI 1: out = acc + bias + res      EPI 2: out = acc + bias
 // NTAP 9: 3x3 convolution with zero padding; NTAP 1: 1x1 convolution (the q/k/v projections of Self_Attention, model.py:294-296)
-template <int S, int CIN, int COUT, bool PRO, int EPI, int NTAP = 9, int NPT = 2, bool SM2 = false>
+// SM2 / SM1: `out2` / `out` slice-major in the conv's row order (the DMA chain's stem; see conv_epilogue)
+template <int S, int CIN, int COUT, bool PRO, int EPI, int NTAP = 9, int NPT = 2, bool SM2 = false, bool SM1 = false>
 // NPT = 3 only pays with two waves per SIMD (<= 256 registers, a handful of spills): measured 132 vs 118 TFLOP/s at one
 __global__ __launch_bounds__(256, (NPT > 2 ? 2 : 1)) void k_conv3x3(const float* __restrict__ in, float* __restrict__ out,
                                                  const float* __restrict__ res, const float* __restrict__ Wt,
@@ -340,9 +360,9 @@ __global__ __launch_bounds__(256, (NPT > 2 ? 2 : 1)) void k_conv3x3(const float*
 #pragma unroll
     for (int t = 0; t < NPT; ++t) {
         mrow[t] = m0 + (wave * NPT + t) * 16 + j;
-        srow[t] = SM2 ? conv_sg_row(mrow[t] / P, mrow[t] % P, P) : mrow[t];
+        srow[t] = SM2 || SM1 ? conv_sg_row(mrow[t] / P, mrow[t] % P, P) : mrow[t];
     }
-    conv_epilogue<COUT, CT, NPT, EPI, false, SM2>(acc, mrow, M, 0, kq, out, res, out2, par, srow, conv_sg_rows(M / P, P));
+    conv_epilogue<COUT, CT, NPT, EPI, SM1, SM2>(acc, mrow, M, 0, kq, out, res, out2, par, srow, conv_sg_rows(M / P, P));
 }
 
 // LDS pointer type of the LDS-DMA builtins; counted wait on the in-order vector-memory counter (loads, stores and LDS-DMA share it)
@@ -378,7 +398,15 @@ __device__ __forceinline__ void tg_dma_buffer(u32x4 rsrc, int voff_bytes, tg_lds
 // conflicted on every read (measured: SQ_LDS_BANK_CONFLICT = 49 % of SQ_LDS_IDX_ACTIVE).
 __device__ __forceinline__ int swz64(int row) { return ((row >> 2) & 1) << 1; }
 
-// ---- F->F 3x3 conv of the f32 tower (F = 128 / 256; input already activated by its producer) -----------------------------------
+// ---- F->F 3x3 conv of the f32 tower (F = 128 / 256) ------------------------------------------------------------------------------
+// SIN: the kernel's stream-side input is the residual stream in the conv's row order (slice-major, board-grouped).  EPI 0: `in` is
+// that stream and s2 / t2 its BN: b = relu(s2 * b + t2) is applied to every B fragment in registers when it is handed over to the
+// next stage (a stage after its load; s2 / t2 of the lane's 4 channels come from `par`, re-read when the slice changes) -- no tap
+// that is walked lies off the board, so there is no zero padding the activation could spoil, and each value is bit for bit the one
+// the producer's epilogue would have stored (bn_relu).  Without SIN `in` is already activated (bufAct).  EPI 1: `res` is the stream,
+// and the accumulators start from it with one 16-B load per lane and (ct, t), a contiguous KB per wave (row-major `res`: sixteen
+// 64-B pieces 81 * 4F bytes apart).  SOUT (EPI 1): `out` is written in the same order, else row-major for an attention layer or
+// the head.
 // Implicit GEMM on v_mfma_f32_16x16x4_f32: D[cout][board] += W[tap][cout][cin] * X[board][pos + tap][cin].
 // Workgroup = ONE board position x 128 boards x all F couts: 4 waves x NPT = 2 tiles, a tile = that position on one group of 16
 // boards (the 16 columns of an MFMA; conv_rows.h has the row order that makes such a tile one contiguous KB per slice).  Which of
@@ -399,10 +427,11 @@ __device__ __forceinline__ int swz64(int row) { return ((row >> 2) & 1) << 1; }
 // MFMA column depends on its own B column only.  The buffer resource ends with the padded tensor, so nothing is read past it.
 // Workgroups are numbered board range major, and inside a range longest walk first (conv_pos_of): the 81 (361) workgroups that
 // share one range's input are neighbours, and each XCD takes a contiguous run of them.
-// F = 128: 95 VGPRs and 34 KB of LDS, four workgroups per CU; F = 256: 159 VGPRs and 67 KB, two per CU.  Three tiles per wave
+// F = 128: 95 VGPRs (96 with SOUT, 104 with the activation on load) and 34 KB of LDS, four workgroups per CU; F = 256: 159 VGPRs (168
+// in the activating kernel only) and 67 KB, two per CU.  Three tiles per wave
 // (192 boards, three workgroups per CU at F = 128), the better shape of the row-ordered kernel on full rounds, measured 4-7 %
 // slower here at 9x9 and 19x19: the walks differ in length, and four shorter waves per SIMD fill each other's gaps better.
-template <int S, int F, int EPI>
+template <int S, int F, int EPI, bool SIN = false, bool SOUT = false>
 __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const float* __restrict__ in, float* __restrict__ out,
                                                                        const float* __restrict__ res, const float* __restrict__ Ws,
                                                                        const float* __restrict__ bias, float* __restrict__ out2,
@@ -426,7 +455,8 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
     const int range = bid / P;
     const int p = conv_pos_of(bid - range * P, S);
     const int M = rows * P, Msm = conv_sg_rows(rows, P);
-    for (int i = tid; i < F; i += 256) { par[i] = bias[i]; par[F + i] = out2 ? s2[i] : 0.f; par[2 * F + i] = out2 ? t2[i] : 0.f; }
+    constexpr bool ACT = EPI == 0 && SIN;                               // s2 / t2 are then the BN of `in`, applied as its fragments land
+    for (int i = tid; i < F; i += 256) { par[i] = bias[i]; par[F + i] = out2 || ACT ? s2[i] : 0.f; par[2 * F + i] = out2 || ACT ? t2[i] : 0.f; }
 
     // the workgroup's walk: nt on-board taps, packed 4 bits each; k / nt by a multiplication that is exact far beyond NSL * 9
     const unsigned mask = conv_tap_mask(p, S);
@@ -455,14 +485,29 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
     const bool active = grp0 * 16 < rows;                               // wave-uniform
     const int boff = ((conv_sg_row(grp0 * 16 + j, p, P)) * CC + kq * 4) * 4;   // byte offset of this lane's 16 B inside slice 0, tile 0
     f32x4 acc[CT][NPT], b_cur[NPT], b_next[NPT];
+    int sl_b = 0, sl_p = -1;                                             // slice of the fragments last loaded / of bsc, bsh (scalars)
+    f32x4 bsc, bsh;                                                      // ACT: s1 / t1 of the lane's 4 channels (slice, kq)
     auto load_b = [&](f32x4* b, int k) {
         int sl, tap;
         stage(k, &sl, &tap);
+        sl_b = sl;
         const int ty = (tap * 11) >> 5;                                  // tap / 3
         const int soff = (sl * Msm + ((ty - 1) * S + (tap - 3 * ty - 1)) * 16) * (CC * 4);   // wave-uniform: slice base + tap shift
 #pragma unroll
         for (int t = 0; t < NPT; ++t)                                    // the offset carries everything: the range check is on it
             b[t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, (int)((unsigned)boff + (unsigned)soff + (unsigned)(t * (P * 16 * CC * 4))), 0, 0));
+    };
+    // b = relu(s1 * b + t1) on the fragments of the stage loaded last; s1 / t1 are re-read from `par` when the slice changes
+    auto act_b = [&](f32x4* dst, const f32x4* b) {
+        if (sl_b != sl_p) {
+            sl_p = sl_b;
+            bsc = *reinterpret_cast<const f32x4*>(par + F + sl_b * CC + kq * 4);
+            bsh = *reinterpret_cast<const f32x4*>(par + 2 * F + sl_b * CC + kq * 4);
+        }
+#pragma unroll
+        for (int t = 0; t < NPT; ++t)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dst[t][e] = bn_relu_unpacked(b[t][e], bsc[e], bsh[e]);
     };
 #pragma unroll
     for (int k = 0; k < D; ++k) dma_w(k);
@@ -470,12 +515,19 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
 #pragma unroll
         for (int t = 0; t < NPT; ++t) {
             const int b = (grp0 + t) * 16 + j;
-            const int m = b < rows ? b * P + p : M - 1;
+            [[maybe_unused]] const int m = b < rows ? b * P + p : M - 1;
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {                            // EPI 1: start from the residual (no loads behind the epilogue's stores)
                 acc[ct][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-                // always issued (boards past the batch re-read the last row; they are never stored): the wait below counts them
-                if (EPI == 1) acc[ct][t] = *reinterpret_cast<const f32x4*>(res + (size_t)m * F + ct * 16 + kq * 4);
+                // always issued (they are never stored for boards past the batch): the wait below counts them
+                if constexpr (EPI == 1 && SIN) {
+                    // the stream in the conv's row order: a (ct, t) is one contiguous KB per wave.  Absent boards of a present group read
+                    // their own never-written rows; a group past the padded tensor reads another slice or, past the end, zeros
+                    const __amdgpu_buffer_rsrc_t rres = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(res), 0, Msm * F * 4, 0x00020000);
+                    acc[ct][t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rres, (int)((unsigned)boff + (unsigned)(ct * Msm * (CC * 4)) + (unsigned)(t * (P * 16 * CC * 4))), 0, 0));
+                } else if constexpr (EPI == 1) {
+                    acc[ct][t] = *reinterpret_cast<const f32x4*>(res + (size_t)m * F + ct * 16 + kq * 4);   // row-major: the last row instead
+                }
             }
         }
         load_b(b_cur, 0);
@@ -488,6 +540,13 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     TG_BARRIER();
+    if constexpr (ACT) {                                                 // `par` is published by the barrier above
+        if (active) act_b(b_cur, b_cur);
+        else {                                                           // written on both paths: the loop then waits for no load of b_cur
+#pragma unroll
+            for (int t = 0; t < NPT; ++t) b_cur[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
 
 #pragma unroll 1
     for (int k0 = 0; k0 < nst; k0 += 2) {
@@ -510,8 +569,13 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
                             acc[ct][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[s4], b_cur[t][s4], acc[ct][t], 0, 0, 0);
                     a_cur = a_next;
                 }
+                if constexpr (ACT) {
+                    __builtin_amdgcn_sched_barrier(0);                   // behind the stage's MFMAs: the fragments are a stage old here
+                    act_b(b_cur, b_next);
+                } else {
 #pragma unroll
-                for (int t = 0; t < NPT; ++t) b_cur[t] = b_next[t];
+                    for (int t = 0; t < NPT; ++t) b_cur[t] = b_next[t];
+                }
             }
             TG_VMCNT(0);                                                 // B fragments of stage k+1 (and any weight pieces): a stage old
         }
@@ -526,7 +590,7 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
         mrow[t] = b < rows ? b * P + p : M;                              // M: not stored
         srow[t] = conv_sg_row(b, p, P);
     }
-    conv_epilogue<F, CT, NPT, (EPI == 1 ? 2 : EPI), EPI == 0, true>(acc, mrow, M, 0, kq, out, res, out2, par, srow, Msm);
+    conv_epilogue<F, CT, NPT, (EPI == 1 ? 2 : EPI), EPI == 0 || SOUT, true>(acc, mrow, M, 0, kq, out, res, out2, par, srow, Msm);
 }
 
 // fp16 activation tensors are CHUNK-MAJOR: [channels/32 slices][4 chunks of 8 channels][M rows][8 halfs].  A slab DMA piece (64 rows
@@ -1979,7 +2043,15 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
 
     // ---- what differs between the chains: stem, residual block, attention block, head conv ----
     float* x = n->bufA; float* y = n->bufB;
-    auto stem = [&](bool act, const float* sn, const float* tn) {   // conv 16 -> F into the residual stream x
+    // The DMA chain's residual stream between two conv layers (stem or residual block -> residual block) is ONE tensor, slice-major
+    // in the conv's row order (conv_rows.h): the producer writes only it (`sout`), the consumer's conv1 activates it on load and its
+    // conv2 starts its accumulators from it (`sin`).  Towards an attention layer or the head the stream is row-major as before, and an
+    // attention layer hands a residual block relu(bn1(.)) in bufAct.  one_stream 2 keeps writing bufAct beside the slice-major stream
+    // (conv1 reads it, nothing is activated on load); 0 is the two-tensor chain.
+    const int one = chain == CHAIN_DMA ? n->path.one_stream : 0;
+    auto conv_layer = [&](size_t j) { return j < nl && n->layers[j].kind == 0; };
+    float* const act2 = one == 1 ? nullptr : n->bufAct;              // relu(bn1_next(.)) beside a conv layer's output
+    auto stem = [&](bool act, const float* sn, const float* tn, bool sout) {   // conv 16 -> F into the residual stream x
         if constexpr (WIDE) {
             if (h16) {   // input planes are 0/1, exact in fp16; 16 planes padded to 64 channels = 18 stages
                 auto* k = x2 ? &k_conv3x3_h2<S, 64, F, 4, false, true> : n->path.r16 ? &k_conv3x3_h2<S, 64, F, 4, true> : &k_conv3x3_h2<S, 64, F, 4>;
@@ -1988,14 +2060,15 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
                 return;
             }
             if (chain == CHAIN_DMA) {
-                hipLaunchKernelGGL((k_conv3x3<S, 16, F, false, 0, 9, 2, true>), dim3(grid), dim3(256), 0, st, n->x0, x, nullptr, n->stem.w,
-                                   n->stem.b, nullptr, nullptr, M, act ? n->bufAct : nullptr, sn, tn);
+                auto* k = sout ? &k_conv3x3<S, 16, F, false, 0, 9, 2, true, true> : &k_conv3x3<S, 16, F, false, 0, 9, 2, true>;
+                hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, n->x0, x, nullptr, n->stem.w,
+                                   n->stem.b, nullptr, nullptr, M, act ? act2 : nullptr, sn, tn);
                 return;
             }
         }
         hipLaunchKernelGGL((k_conv3x3<S, 16, F, false, 0>), dim3(grid), dim3(256), 0, st, n->x0, x, nullptr, n->stem.w, n->stem.b, nullptr, nullptr, M);
     };
-    auto block = [&](const BlockW& b, int ridx, float* out, bool act, const float* sn, const float* tn) {   // y = x + conv(conv(x))
+    auto block = [&](const BlockW& b, int ridx, float* out, bool act, const float* sn, const float* tn, bool sin, bool sout) {   // y = x + conv(conv(x))
         if constexpr (WIDE) {
             if (h16) {
                 auto* k1 = x2 ? &k_conv3x3_h2<S, 2 * F, F, 0, false, true> : &k_conv3x3_h2<S, F, F, 0>;
@@ -2011,12 +2084,15 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
             if (chain == CHAIN_DMA) {
                 // one workgroup per (range of 128 boards, position), the count rounded up to the XCD-contiguous order's multiple of 8
                 const int grid_sd = ((rows + 127) / 128 * P + 7) / 8 * 8;
-                auto* k1 = &k_conv3x3_sg<S, F, 0>;
-                auto* k2 = &k_conv3x3_sg<S, F, 1>;
+                const bool onload = sin && one == 1;                 // conv1 reads the stream itself, else its activated copy
+                auto* k1 = onload ? &k_conv3x3_sg<S, F, 0, true> : &k_conv3x3_sg<S, F, 0>;
+                auto* k2 = sin ? (sout ? &k_conv3x3_sg<S, F, 1, true, true> : &k_conv3x3_sg<S, F, 1, true, false>)
+                               : (sout ? &k_conv3x3_sg<S, F, 1, false, true> : &k_conv3x3_sg<S, F, 1>);
                 { ProfScope ps(n, st, conv_flops);
-                  hipLaunchKernelGGL(k1, dim3(grid_sd), dim3(256), 0, st, n->bufAct, n->bufH, nullptr, b.g1, b.c1.b, nullptr, nullptr, nullptr, rows); }
+                  hipLaunchKernelGGL(k1, dim3(grid_sd), dim3(256), 0, st, onload ? x : n->bufAct, n->bufH, nullptr, b.g1, b.c1.b, nullptr,
+                                     onload ? b.s1 : nullptr, onload ? b.t1 : nullptr, rows); }
                 { ProfScope ps(n, st, conv_flops);
-                  hipLaunchKernelGGL(k2, dim3(grid_sd), dim3(256), 0, st, n->bufH, out, x, b.g2, b.c2.b, act ? n->bufAct : nullptr, sn, tn, rows); }
+                  hipLaunchKernelGGL(k2, dim3(grid_sd), dim3(256), 0, st, n->bufH, out, x, b.g2, b.c2.b, act ? act2 : nullptr, sn, tn, rows); }
                 return;
             }
         }
@@ -2103,15 +2179,18 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
         else hipLaunchKernelGGL((k_obs_to_rows<S>), dim3(g0), dim3(256), 0, st, obs, n->x0, rows, n->C);
     }
     const float* sn; const float* tn;
-    { const bool act = next_bn(0, &sn, &tn); stem(act, sn, tn); }
+    bool sm = one && conv_layer(0);                    // x is slice-major in the conv's row order
+    { const bool act = next_bn(0, &sn, &tn); stem(act, sn, tn, sm); }
     for (size_t i = 0; i < nl; ++i) {
         const Layer& L = n->layers[i];
         const bool act = next_bn(i + 1, &sn, &tn);
+        const bool sin = sm;
+        sm = one && L.kind == 0 && conv_layer(i + 1);
         if (L.kind == 1) {
             if (attention(L.a, x, y, nullptr, nullptr, act, sn, tn)) TG_FAIL(ctx, TG_ERR_ARG, "attention blocks: no kernel for this shape and precision (built: f32 at 9x9 with 32 / 64 / 128 / 256 filters and at 19x19 with 128 / 256, f16 at 9x9 with 128, f32x3 at 9x9 with 128 / 256)");
         } else {
             // nothing reads the last block's f32 stream when the head conv takes act16 and no policy attention follows
-            block(n->blocks[L.ridx], L.ridx, i + 1 == nl && head16 && !n->pol_att ? nullptr : y, act, sn, tn);
+            block(n->blocks[L.ridx], L.ridx, i + 1 == nl && head16 && !n->pol_att ? nullptr : y, act, sn, tn, sin, sm);
         }
         float* t = x; x = y; y = t;
     }
@@ -2332,6 +2411,8 @@ NetPath net_path(int S, int F, int prec, const std::string& trunk, bool pol) {
     else if (F == 128 || F == 256) {                                    // attention layers: k_attention_mfma (9x9), k_attention_t (19x19)
         const char* dma = getenv("TG_DMA_CONV");
         p.chain = dma && atoi(dma) == 0 ? CHAIN_F32 : CHAIN_DMA;
+        const char* one = getenv("TG_ONE_STREAM");                      // 0: two tensors (the A/B arm); 2: one stream, bufAct kept
+        p.one_stream = one && one[0] >= '0' && one[0] <= '2' && !one[1] ? one[0] - '0' : 1;   // anything but one digit 0..2: the default
     }
     p.r16 = prec == 2;
     p.att_x3 = prec == 3 && any_att && F == 128 && S == 9;
@@ -2393,10 +2474,11 @@ int tg_net_load_arch(tg_ctx* ctx, const char* arch_c, const float* blob, size_t 
         const NetPath& p = n->path = net_path(S, F, prec, trunk, pol);
         const bool h16 = p.chain == CHAIN_F16 || p.chain == CHAIN_SPLIT, x2 = p.chain == CHAIN_SPLIT;
         const size_t act = sizeof(float) * (size_t)rows_cap * P * F;
-        TG_HIP(ctx, hipMalloc((void**)&n->bufA, act));
-        TG_HIP(ctx, hipMalloc((void**)&n->bufB, act));
-        // bufH and bufAct are slice-major in the DMA chain: whole groups of 16 boards (conv_rows.h), the padding never written
+        // bufH and bufAct are slice-major in the DMA chain: whole groups of 16 boards (conv_rows.h), the padding never written; so is
+        // the residual stream between two conv layers there (bufA / bufB hold it in either layout)
         const size_t act_sm = sizeof(float) * (size_t)conv_sg_rows(rows_cap, (int)P) * F;
+        TG_HIP(ctx, hipMalloc((void**)&n->bufA, p.chain == CHAIN_DMA ? act_sm : act));
+        TG_HIP(ctx, hipMalloc((void**)&n->bufB, p.chain == CHAIN_DMA ? act_sm : act));
         TG_HIP(ctx, hipMalloc((void**)&n->bufH, act_sm));
         TG_HIP(ctx, hipMalloc((void**)&n->x0, sizeof(float) * (size_t)rows_cap * P * 16));
         TG_HIP(ctx, hipMalloc((void**)&n->hc, sizeof(float) * (size_t)rows_cap * P * 16));
@@ -2407,7 +2489,8 @@ int tg_net_load_arch(tg_ctx* ctx, const char* arch_c, const float* blob, size_t 
         if (any_att && !p.att_h) TG_HIP(ctx, hipMalloc((void**)&n->bufQ, sizeof(float) * (size_t)rows_cap * P * Wq));
         if (pol) TG_HIP(ctx, hipMalloc((void**)&n->hca, sizeof(float) * (size_t)rows_cap * P * 16));
         const size_t wcopy = (size_t)(NB > 0 ? 2 * NB : 1) * 9 * F * F;
-        if (p.chain == CHAIN_DMA) TG_HIP(ctx, hipMalloc((void**)&n->bufAct, act_sm));
+        // relu(bn1(.)) beside the stream: only an attention layer hands it to a residual block once the conv layers share one stream
+        if (p.chain == CHAIN_DMA && (p.one_stream != 1 || trunk.find("AR") != std::string::npos)) TG_HIP(ctx, hipMalloc((void**)&n->bufAct, act_sm));
         for (Net::WeightSet& w : n->sets) {
             TG_HIP(ctx, hipMalloc((void**)&w.blob, sizeof(float) * n_floats));
             TG_HIP(ctx, hipMalloc((void**)&w.head_g, sizeof(float) * 64 * (size_t)F));
@@ -2600,6 +2683,14 @@ int tg_net_predict(tg_ctx* ctx, const float* obs, int n_rows, float* policy, flo
 // tiles (convs) / boards (attention) in which a value beyond +-65504 was rounded to fp16 -- from there on the network computes
 // inf / NaN; 0 = every forward pass so far stayed in range.  Always 0 with net_precision 0.  weight_absmax: largest |w| of the
 // live weight set's BN-folded blob (inf / NaN if the blob holds one).  A non-zero count also leaves a message in tg_last_error.
+int tg_net_stream_layout(tg_ctx* ctx, int* one_stream, int* act_copy) {
+    if (!ctx || !ctx->eng || !ctx->eng->net) return TG_ERR_STATE;
+    const Net* n = ctx->eng->net;
+    if (one_stream) *one_stream = n->path.chain == CHAIN_DMA ? n->path.one_stream : 0;
+    if (act_copy) *act_copy = n->bufAct != nullptr;
+    return TG_OK;
+}
+
 int tg_net_range(tg_ctx* ctx, uint64_t* fp16_overflows, float* weight_absmax) {
     if (!ctx || !ctx->eng || !ctx->eng->net) return TG_ERR_STATE;
     Net* n = ctx->eng->net;
