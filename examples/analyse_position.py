@@ -1,0 +1,36 @@
+#!/usr/bin/env python3
+"""Analyse a position: play a few moves with GoEnv, search the position with a (random-weight) network and print what the
+search thinks -- per candidate move its visits, value and prior, and the line it expects.
+
+    python examples/analyse_position.py            # needs an MI355X; a few seconds
+"""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from transgo_amd import analysis, model                           # noqa: E402
+from transgo_amd.engine import SelfPlayEngine                     # noqa: E402
+from transgo_amd.environment import GoEnv                         # noqa: E402
+
+
+def main(moves=("E5", "C3", "G7", "C7"), sims=200, filters=32, blocks=2, board_size=9):
+    env = GoEnv(board_size=board_size)
+    state, _ = env.reset()
+    names = {analysis.vertex(a, board_size): a for a in range(board_size ** 2 + 1)}
+    for m in moves:
+        state, done = env.step(state, names[m])
+        assert not done
+    env.show(state)
+    eng = SelfPlayEngine(1, board_size=board_size, num_simulation=sims, net_blocks=blocks, net_filters=filters)
+    model.load_into(eng.ctx, model.random_weights(board_size, 10, filters, blocks, seed=3), board_size, 10, filters, blocks)
+    eng.reset([0])                                                # seeds the stream the search's tie breaks draw from
+    rec = analysis.analyse(eng, np.frombuffer(state, np.uint8).reshape(1, -1))[0]
+    print(analysis.format_analysis(rec, board_size, top=8))
+    eng.close()
+    return rec
+
+
+if __name__ == "__main__":
+    main()

@@ -158,6 +158,45 @@ int tg_sp_search(tg_ctx* ctx, int32_t* n_waves);
  * (self_play.py:685).  Any pointer may be NULL. */
 int tg_sp_root_info(tg_ctx* ctx, int32_t* visits /*[G][A]*/, int32_t* root_n, int32_t* player, int32_t* step,
                     float* obs /*[G][C][S][S]*/);
+/* ---- search tree read-out (analysis, play against a person, debugging a weight set) ------------------------------------------
+ * Both calls only READ the trees: they are legal at any point between engine calls, also between tg_sp_collect and
+ * tg_sp_absorb (pending counters are then reported as they stand), and leave the search, the RNG streams and a pending batch
+ * untouched.  Every tree reference they follow is range-checked first, so a damaged tree yields a status, never a bad address. */
+
+/* bits of tg_sp_root_children's flags[g][a] */
+#define TG_CHILD_PRESENT 0x01u  /* the root has a child for action a, i.e. a is legal at the root (self_play.py:603) */
+#define TG_CHILD_OPEN    0x02u  /* real_expanded (self_play.py:62): the child was evaluated and has children of its own */
+#define TG_CHILD_PRIOR32 0x04u  /* prior[g][a] is a float32 value widened (a network prior); clear: float64 (after root noise) */
+#define TG_CHILD_WIN     0x08u  /* the move ends the game and the cached result (self_play.py:638-642) is +1 for the side to move there */
+#define TG_CHILD_LOSS    0x10u  /* ... or -1 */
+/* tg_sp_root_children's status[g] */
+enum {
+    TG_ROOT_OK = 0,
+    TG_ROOT_PARKED = 1,         /* slot left out by tg_sp_reset_from's mask: rows and root values are all zero */
+    TG_ROOT_UNEVALUATED = 2,    /* the root awaits evaluation (tg_sp_expand_roots not called yet): no children yet */
+    TG_ROOT_TERMINAL = 3,       /* the root position is the end of the game: no children */
+    TG_ROOT_ERROR = 4           /* the game is parked in error (tg_sp_game_errors), or its tree failed a range check: all zero */
+};
+/* The root's children as dense per-action tables -- the fields of Node_V (self_play.py:51-63) of every entry of
+ * root.children (self_play.py:70-77): n = total_visit_count (:55), pending = ons (:56, the WU-UCT counter of :767-774),
+ * w = value_sum (:57) and var = value_var (:59) as stored in float32, prior (:54; after root noise, :90-95, a float64),
+ * flags = the TG_CHILD_* bits.  The value of move a from the mover's side is -(w / (n + 1)) in float32, the value_score term of
+ * ucb_score (:67-68, :716-725).  Per game: the root record's own n / pending / w / var (w / (n + 1) = the root's value from the
+ * side to move) and status = TG_ROOT_*.  Every one of the A entries of a game is written: absent actions, and all
+ * rows of a game whose status is not TG_ROOT_OK, are 0.  Any pointer may be NULL: it is then neither computed nor copied. */
+int tg_sp_root_children(tg_ctx* ctx, int32_t* n /*[G][A]*/, int32_t* pending /*[G][A]*/, float* w /*[G][A]*/,
+                        float* var /*[G][A]*/, double* prior /*[G][A]*/, uint8_t* flags /*[G][A]*/, int32_t* root_n /*[G]*/,
+                        int32_t* root_pending /*[G]*/, float* root_w /*[G]*/, float* root_var /*[G]*/, uint8_t* status /*[G]*/);
+/* Principal variation: from the root, the child with the most visits (ties: the lowest action, i.e. the first in the order of
+ * the `children` dict, self_play.py:603 -- ascending action, pass last), down to `depth` levels (1 .. the path capacity,
+ * max_step + 2 rounded up to 64; anything else is TG_ERR_ARG).  The walk ends early at a node that has no children, that is only
+ * pseudo-expanded (self_play.py:634-636: evaluation pending) or whose best child was never visited.  action i32[G][depth]
+ * (padding -1), n i32[G][depth] and w f32[G][depth] (the chosen child's total_visit_count / value_sum; padding 0), len i32[G] =
+ * levels found; 0 for a parked, finished or errored slot, -1 when the walk met a reference that failed its range check (the row
+ * is then all padding).  Any output pointer may be NULL. */
+int tg_sp_pv(tg_ctx* ctx, int depth, int32_t* action /*[G][depth]*/, int32_t* n /*[G][depth]*/, float* w /*[G][depth]*/,
+             int32_t* len /*[G]*/);
+
 /* One random_sample() from each game's stream: the draw inside np.random.choice(A, p=) (self_play.py:683). */
 int tg_sp_draw_uniform(tg_ctx* ctx, double* u /*[G]*/, const uint8_t* mask);
 int tg_sp_rng_state(tg_ctx* ctx, int game, tg_mt19937* out);

@@ -1,0 +1,79 @@
+"""Position analysis on top of the tree read-out (tg_sp_root_children, tg_sp_pv): what a person looking at a position, a GTP
+front end or somebody debugging a weight set asks a search for -- per candidate move its visits, value and prior, the root's own
+value and the line the search expects.  The reference has no such interface of its own; its consumers of these numbers are
+human_play.py and elo.py, which read them off the Node_V objects (self_play.py:51-95) directly.
+"""
+import numpy as np
+
+_COLUMNS = "ABCDEFGHJKLMNOPQRST"           # GTP column letters: no I
+
+
+def vertex(action, board_size):
+    """GTP vertex of an action: column letter (I skipped) + row number counted from the bottom, so row index 0 of the action
+    grid (action // board_size) is row `board_size`; board_size**2 is "pass"."""
+    action, S = int(action), int(board_size)
+    if action == S * S:
+        return "pass"
+    if not 0 <= action < S * S:
+        raise ValueError(f"action {action} is not on a {S}x{S} board")
+    return f"{_COLUMNS[action % S]}{S - action // S}"
+
+
+def analyse(engine, states, num_simulation=0, depth=16):
+    """Search every position of `states` ([N, state_size] uint8 blobs of transgo_amd.environment.GoEnv) in evaluation mode -- a
+    fresh root, no root noise, as select_action's prologue (self_play.py:689-700) -- and read the trees out.  The engine's games
+    are re-rooted (`reset_from`), so whatever they held is gone; the engine must have been `reset` once before (that seeds the
+    streams the tie breaks draw from).  More positions than the engine has games go in successive chunks.  num_simulation 0 =
+    the engine's own.  One dict per position:
+      visits  int32[A]    visit count of each move           prior  float64[A]  its prior (0 where the move is illegal)
+      q       float32[A]  value of the move from the mover's side, -(w / (n + 1)) in float32 -- the value_score term of
+                          ucb_score (self_play.py:67-68, :716-725); NaN where the move is illegal or was never visited
+      legal   bool[A]     the move is a child of the root    status  ROOT_* of SelfPlayEngine (0 = searched)
+      root_value  float   w / (n + 1) of the root, from the side to move (NaN unless status is 0)
+      pv      list of actions, most-visited child at each level (ties: lowest action), at most `depth`; pv_visits their visits
+    """
+    states = np.ascontiguousarray(states, np.uint8)
+    if states.ndim != 2:
+        raise ValueError("states must be [N, state_size]")
+    G, N = engine.G, states.shape[0]
+    out = []
+    for lo in range(0, N, G):
+        k = min(G, N - lo)
+        batch = np.repeat(states[lo:lo + 1], G, axis=0)              # slots past the chunk hold a copy and are masked out (parked)
+        batch[:k] = states[lo:lo + k]
+        mask = np.zeros(G, np.uint8); mask[:k] = 1
+        engine.reset_from(batch, None if k == G else mask)
+        engine.search(selfplay=False, num_simulation=num_simulation)
+        rc = engine.root_children()
+        act, vis, _, ln = engine.principal_variation(depth)
+        for g in range(k):
+            present = (rc["flags"][g] & engine.CHILD_PRESENT) != 0
+            n, w = rc["n"][g], rc["w"][g]
+            q = np.full(engine.A, np.nan, np.float32)
+            seen = present & (n > 0)
+            q[seen] = -(w[seen] / (n[seen] + 1).astype(np.float32))
+            ok = rc["status"][g] == engine.ROOT_OK
+            root_value = float(rc["root_w"][g] / np.float32(rc["root_n"][g] + 1)) if ok else float("nan")
+            m = max(int(ln[g]), 0)
+            out.append(dict(visits=n.copy(), prior=rc["prior"][g].copy(), q=q, legal=present, status=int(rc["status"][g]),
+                            root_value=root_value, pv=[int(a) for a in act[g, :m]], pv_visits=[int(v) for v in vis[g, :m]]))
+    return out
+
+
+def format_analysis(record, board_size, top=5):
+    """A table of the `top` candidate moves of one `analyse` record: one line per candidate in descending visits (ties: ascending
+    action) with its vertex, visits, q, prior and its line -- the principal variation for the move that heads it, the move alone
+    for the others.  A q that is NaN (never visited) prints as '-'."""
+    visits, prior, q = np.asarray(record["visits"]), np.asarray(record["prior"]), np.asarray(record["q"])
+    legal = np.asarray(record["legal"]) if "legal" in record else (visits > 0) | (prior > 0)
+    cand = sorted(np.flatnonzero(legal), key=lambda a: (-int(visits[a]), int(a)))[:max(int(top), 0)]
+    pv = list(record.get("pv", []))
+    rv = record.get("root_value", float("nan"))
+    lines = [f"root value {'-' if np.isnan(rv) else format(rv, '+.3f')}   visits {int(visits.sum())}",
+             f"{'move':<5}{'visits':>8}{'q':>8}{'prior':>8}  pv"]
+    for a in cand:
+        qs = "-" if np.isnan(q[a]) else format(float(q[a]), "+.3f")
+        line = pv if pv and pv[0] == a else [a]
+        lines.append(f"{vertex(a, board_size):<5}{int(visits[a]):>8}{qs:>8}{float(prior[a]):>8.4f}  "
+                     + " ".join(vertex(m, board_size) for m in line))
+    return "\n".join(lines)

@@ -66,6 +66,7 @@ struct Engine {
     int32_t* d_fin = nullptr;        // [2][G] device copy of fin_slot / fin_off
     DevBuf hv_obs, hv_cnt, hv_z, hv_own, hv_pl, hv_game;   // harvest staging when the caller wants host arrays
     DevBuf obs_f32;                  // float planes of the pending batch, only materialised for tg_sp_batch_obs (tests, host evaluators)
+    DevBuf readout;                  // staging of tg_sp_root_children / tg_sp_pv, allocated by the first such call
     std::vector<double> h_noise;
     std::vector<int32_t> h_nchild;
     Net* net = nullptr;

@@ -550,6 +550,168 @@ __global__ __launch_bounds__(64) void k_root_info(EngineDev d, int32_t* visits, 
     }
 }
 
+// ---- tree read-out (tg_sp_root_children, tg_sp_pv) ---------------------------------------------------------------------------
+// Read-only walks for analysis: no BoardWave, no LDS, no private arrays.  Unlike the search kernels they may be pointed at a tree
+// they know nothing about (a slot in error, a parked slot, a tree between collect and absorb), so every reference is checked
+// against the pool before it is followed: a record index must lie in [0, pool_slots), a block's header and its nchild <= A child
+// records must lie inside the pool, and an action must be < A before it indexes an output row.
+template <int S> __device__ __forceinline__ bool block_in_pool(const SearchCfg& sc, int blk) {
+    return blk >= 0 && blk <= sc.pool_slots - TreeGeo<S>::HS;
+}
+// the child count of block `blk` (header inside the pool), or -1 when it is not in [0, A] or the child run leaves the pool
+template <int S> __device__ __forceinline__ int checked_nchild(NodeRec* arena, const SearchCfg& sc, int blk) {
+    const int nchild = __builtin_amdgcn_readfirstlane(hdr_of<S>(arena, blk)->nchild);
+    if (nchild < 0 || nchild > Geo<S>::A || nchild > sc.pool_slots - TreeGeo<S>::HS - blk) return -1;
+    return nchild;
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off; off >>= 1) { const unsigned long long o = __shfl_xor(v, off); v = o > v ? o : v; }
+    return v;
+}
+
+// What kind of slot game g is right now (TG_ROOT_*), and its root record / root block when they passed their checks.
+template <int S>
+__device__ __forceinline__ int root_status(const EngineDev& d, int g, NodeRec& rec, int& blk) {
+    const GameCtl* c = &d.ctl[g];
+    const SearchCfg& sc = d.sc;
+    blk = -1;
+    if (__builtin_amdgcn_readfirstlane(c->error)) return TG_ROOT_ERROR;
+    const int root = __builtin_amdgcn_readfirstlane(c->root);
+    if (root < 0 || root >= sc.pool_slots) return TG_ROOT_ERROR;
+    rec = d.arena[root];
+    blk = __builtin_amdgcn_readfirstlane(rec.block);
+    if (blk != -1 && !block_in_pool<S>(sc, blk)) { blk = -1; return TG_ROOT_ERROR; }
+    if (__builtin_amdgcn_readfirstlane(c->finished)) {                // game over, or a slot k_reset parked (its old tree still stands)
+        const bool over = blk >= 0 && hdr_of<S>(d.arena, blk)->st.terminated != 0;
+        return over ? TG_ROOT_TERMINAL : TG_ROOT_PARKED;
+    }
+    if (blk < 0 || !(rec.flags & F_OPEN)) return TG_ROOT_UNEVALUATED;  // self_play.py:599-605 not done yet
+    return TG_ROOT_OK;
+}
+
+// Dense per-action tables of the root's children + the root's own record (tg_sp_root_children).  Lanes go over the children in
+// passes of 64: the reads are the contiguous nchild*32 B run of the root's block; every output pointer may be null.
+template <int S>
+__global__ __launch_bounds__(64) void k_root_children(EngineDev d, int32_t* o_n, int32_t* o_pending, float* o_w, float* o_var, double* o_prior,
+                                                      uint8_t* o_flags, int32_t* root_n, int32_t* root_pending, float* root_w, float* root_var,
+                                                      uint8_t* status) {
+    using G = Geo<S>;
+    constexpr int HS = TreeGeo<S>::HS;
+    const int g = blockIdx.x, lane = lane_id();
+    NodeRec* arena = d.arena;
+    const size_t row = (size_t)g * G::A;
+    auto zero_rows = [&]() {
+        for (int a = lane; a < G::A; a += 64) {
+            if (o_n) o_n[row + a] = 0;
+            if (o_pending) o_pending[row + a] = 0;
+            if (o_w) o_w[row + a] = 0.f;
+            if (o_var) o_var[row + a] = 0.f;
+            if (o_prior) o_prior[row + a] = 0.0;
+            if (o_flags) o_flags[row + a] = 0;
+        }
+    };
+    NodeRec rec; rec.n = 0; rec.pending = 0; rec.w = 0.f; rec.var = 0.f; rec.flags = 0;
+    int blk;
+    int st = root_status<S>(d, g, rec, blk);
+    zero_rows();                                                       // absent actions; the whole row unless the status is OK
+    if (st == TG_ROOT_OK) {
+        const int nchild = checked_nchild<S>(arena, d.sc, blk);
+        if (nchild < 0) st = TG_ROOT_ERROR;
+        __syncthreads();                                               // the zeros are written before a child's entry is
+        bool bad = false;
+        for (int j0 = 0; j0 < nchild; j0 += 64) {
+            const int i = j0 + lane;
+            if (i >= nchild) continue;
+            const NodeRec r = arena[blk + HS + i];
+            const int a = r.action;
+            if (a >= G::A) { bad = true; continue; }
+            if (o_n) o_n[row + a] = r.n;
+            if (o_pending) o_pending[row + a] = r.pending;
+            if (o_w) o_w[row + a] = r.w;
+            if (o_var) o_var[row + a] = r.var;
+            if (o_prior) o_prior[row + a] = r.prior;
+            if (o_flags) o_flags[row + a] = (uint8_t)(TG_CHILD_PRESENT | ((r.flags & F_OPEN) ? TG_CHILD_OPEN : 0u) | ((r.flags & F_PRIOR32) ? TG_CHILD_PRIOR32 : 0u) |
+                                                      (r.term == 1 ? TG_CHILD_WIN : r.term == 2 ? TG_CHILD_LOSS : 0u));
+        }
+        if (ballot64(bad)) {                                           // an action outside the board: the tree is damaged
+            st = TG_ROOT_ERROR;
+            __syncthreads();
+            zero_rows();
+        }
+    }
+    if (lane == 0) {
+        const bool show = st == TG_ROOT_OK || st == TG_ROOT_UNEVALUATED || st == TG_ROOT_TERMINAL;
+        if (root_n) root_n[g] = show ? rec.n : 0;
+        if (root_pending) root_pending[g] = show ? rec.pending : 0;
+        if (root_w) root_w[g] = show ? rec.w : 0.f;
+        if (root_var) root_var[g] = show ? rec.var : 0.f;
+        if (status) status[g] = (uint8_t)st;
+    }
+}
+
+// Principal variation (tg_sp_pv): at each level the child with the most visits, ties to the lowest child index (= lowest action:
+// children are stored in ascending action order, pass last).  A lane keeps the best of the children it saw over the passes as a
+// packed key (visits << 32 | ~index); one wave reduction picks the winner, whose record is then broadcast from the lane that
+// holds it -- one dependent HBM round trip per level, as in k_collect's selection.
+template <int S>
+__global__ __launch_bounds__(64) void k_tree_pv(EngineDev d, int D, int32_t* o_action, int32_t* o_n, float* o_w, int32_t* o_len) {
+    constexpr int HS = TreeGeo<S>::HS;
+    const int g = blockIdx.x, lane = lane_id();
+    NodeRec* arena = d.arena;
+    const size_t row = (size_t)g * D;
+    for (int l = lane; l < D; l += 64) {
+        if (o_action) o_action[row + l] = -1;
+        if (o_n) o_n[row + l] = 0;
+        if (o_w) o_w[row + l] = 0.f;
+    }
+    NodeRec cur; cur.flags = 0; cur.block = -1;
+    int blk;
+    const int st = root_status<S>(d, g, cur, blk);
+    int len = 0;
+    bool damaged = false;
+    if (st == TG_ROOT_OK) {
+        __syncthreads();                                               // the padding is written before a level's entry is
+        while (len < D && (cur.flags & F_OPEN)) {
+            blk = __builtin_amdgcn_readfirstlane(cur.block);
+            if (blk == -1) break;
+            if (!block_in_pool<S>(d.sc, blk)) { damaged = true; break; }
+            const int nchild = checked_nchild<S>(arena, d.sc, blk);
+            if (nchild < 0) { damaged = true; break; }
+            unsigned long long key = 0;                                // 0 = no child seen (a real key has ~index != 0 in its low word)
+            NodeRec mine = cur;
+            for (int j0 = 0; j0 < nchild; j0 += 64) {
+                const int i = j0 + lane;
+                if (i >= nchild) continue;
+                const NodeRec r = arena[blk + HS + i];
+                const unsigned long long k = ((unsigned long long)(uint32_t)(r.n < 0 ? 0 : r.n) << 32) | (uint32_t)~(uint32_t)i;
+                if (k > key) { key = k; mine = r; }
+            }
+            const unsigned long long best = wave_max_u64(key);
+            if ((best >> 32) == 0) break;                              // no children, or the best child was never visited
+            const uint64_t who = ballot64(key == best);                // exactly one lane: indices are distinct
+            cur = bcast_rec(mine, __builtin_amdgcn_readfirstlane(__ffsll((long long)who) - 1));
+            if (cur.action >= d.sc.A) { damaged = true; break; }
+            if (lane == 0) {
+                if (o_action) o_action[row + len] = cur.action;
+                if (o_n) o_n[row + len] = cur.n;
+                if (o_w) o_w[row + len] = cur.w;
+            }
+            ++len;
+        }
+    }
+    if (damaged) {
+        __syncthreads();
+        for (int l = lane; l < D; l += 64) {
+            if (o_action) o_action[row + l] = -1;
+            if (o_n) o_n[row + l] = 0;
+            if (o_w) o_w[row + l] = 0.f;
+        }
+        len = -1;
+    }
+    if (lane == 0 && o_len) o_len[g] = len;
+}
+
 // update_with_action (self_play.py:857-872) + tree compaction into the other half arena.
 // Before the root moves on, the game's record gets this move's entry -- env.encode(root) bit-packed, the raw visit counts and
 // the side to move: what self_play.py:917-926 appends to its three Python lists.
@@ -1002,7 +1164,7 @@ void tg_engine_destroy(tg_ctx* ctx) {
                     e->d_fin, e->dev.hist_obs, e->dev.hist_cnt, e->dev.hist_pl};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->h_rng) (void)hipHostFree(e->h_rng);
-    e->obs_f32.release(); e->hv_obs.release(); e->hv_cnt.release(); e->hv_z.release(); e->hv_own.release(); e->hv_pl.release(); e->hv_game.release();
+    e->obs_f32.release(); e->readout.release(); e->hv_obs.release(); e->hv_cnt.release(); e->hv_z.release(); e->hv_own.release(); e->hv_pl.release(); e->hv_game.release();
     for (hipEvent_t ev : e->tev) (void)hipEventDestroy(ev);
     tg_net_destroy(ctx);
     delete e;
@@ -1253,6 +1415,68 @@ int tg_sp_root_info(tg_ctx* ctx, int32_t* visits, int32_t* root_n, int32_t* play
     if (player) TG_HIP(ctx, hipMemcpyAsync(player, d_pl, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
     if (step) TG_HIP(ctx, hipMemcpyAsync(step, d_st, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
     if (obs) TG_HIP(ctx, hipMemcpyAsync(obs, d_obs, sizeof(float) * (size_t)G * C * P, hipMemcpyDeviceToHost, ctx->stream));
+    TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return TG_OK;
+}
+
+// The read-out entry points name what is wrong with the context (NEED_ENGINE returns a bare TG_ERR_ARG).
+#define NEED_READOUT(ctx, who)                                                                                             \
+    do {                                                                                                                   \
+        if (!(ctx)) return TG_ERR_ARG;                                                                                     \
+        if (!(ctx)->eng || (ctx)->eng->G <= 0) TG_FAIL(ctx, TG_ERR_ARG, who ": the context has no engine (n_games == 0)"); \
+        if (!(ctx)->eng->all_reset) TG_FAIL(ctx, TG_ERR_STATE, who ": no game has a tree yet (call tg_sp_reset first)");   \
+        TG_HIP(ctx, hipSetDevice((ctx)->cfg.device));                                                                      \
+    } while (0)
+
+int tg_sp_root_children(tg_ctx* ctx, int32_t* n, int32_t* pending, float* w, float* var, double* prior, uint8_t* flags,
+                        int32_t* root_n, int32_t* root_pending, float* root_w, float* root_var, uint8_t* status) {
+    NEED_READOUT(ctx, "tg_sp_root_children");
+    Engine* e = ctx->eng;
+    const size_t G = (size_t)e->G, GA = G * ctx->A;
+    // staging, widest type first: prior f64[G][A] | n, pending i32[G][A] | w, var f32[G][A] | root n, pending, w, var [G] | flags u8[G][A] | status u8[G]
+    if (e->readout.reserve(GA * 25 + G * 17)) TG_FAIL(ctx, TG_ERR_HIP, "hipMalloc failed");
+    double* d_prior = (double*)e->readout.p;
+    int32_t* d_n = (int32_t*)(d_prior + GA); int32_t* d_pend = d_n + GA;
+    float* d_w = (float*)(d_pend + GA); float* d_var = d_w + GA;
+    int32_t* d_rn = (int32_t*)(d_var + GA); int32_t* d_rp = d_rn + G;
+    float* d_rw = (float*)(d_rp + G); float* d_rv = d_rw + G;
+    uint8_t* d_flags = (uint8_t*)(d_rv + G); uint8_t* d_status = d_flags + GA;
+    TG_LAUNCH(ctx, k_root_children, e->G, e->dev, n ? d_n : nullptr, pending ? d_pend : nullptr, w ? d_w : nullptr, var ? d_var : nullptr,
+              prior ? d_prior : nullptr, flags ? d_flags : nullptr, root_n ? d_rn : nullptr, root_pending ? d_rp : nullptr,
+              root_w ? d_rw : nullptr, root_var ? d_rv : nullptr, status ? d_status : nullptr);
+    if (n) TG_HIP(ctx, hipMemcpyAsync(n, d_n, sizeof(int32_t) * GA, hipMemcpyDeviceToHost, ctx->stream));
+    if (pending) TG_HIP(ctx, hipMemcpyAsync(pending, d_pend, sizeof(int32_t) * GA, hipMemcpyDeviceToHost, ctx->stream));
+    if (w) TG_HIP(ctx, hipMemcpyAsync(w, d_w, sizeof(float) * GA, hipMemcpyDeviceToHost, ctx->stream));
+    if (var) TG_HIP(ctx, hipMemcpyAsync(var, d_var, sizeof(float) * GA, hipMemcpyDeviceToHost, ctx->stream));
+    if (prior) TG_HIP(ctx, hipMemcpyAsync(prior, d_prior, sizeof(double) * GA, hipMemcpyDeviceToHost, ctx->stream));
+    if (flags) TG_HIP(ctx, hipMemcpyAsync(flags, d_flags, GA, hipMemcpyDeviceToHost, ctx->stream));
+    if (root_n) TG_HIP(ctx, hipMemcpyAsync(root_n, d_rn, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
+    if (root_pending) TG_HIP(ctx, hipMemcpyAsync(root_pending, d_rp, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
+    if (root_w) TG_HIP(ctx, hipMemcpyAsync(root_w, d_rw, sizeof(float) * G, hipMemcpyDeviceToHost, ctx->stream));
+    if (root_var) TG_HIP(ctx, hipMemcpyAsync(root_var, d_rv, sizeof(float) * G, hipMemcpyDeviceToHost, ctx->stream));
+    if (status) TG_HIP(ctx, hipMemcpyAsync(status, d_status, G, hipMemcpyDeviceToHost, ctx->stream));
+    TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return TG_OK;
+}
+
+int tg_sp_pv(tg_ctx* ctx, int depth, int32_t* action, int32_t* n, float* w, int32_t* len) {
+    NEED_READOUT(ctx, "tg_sp_pv");
+    Engine* e = ctx->eng;
+    if (depth < 1 || depth > e->dev.sc.maxd) {
+        char msg[96];
+        snprintf(msg, sizeof(msg), "tg_sp_pv: depth must be 1..%d (the path capacity), got %d", e->dev.sc.maxd, depth);
+        TG_FAIL(ctx, TG_ERR_ARG, msg);
+    }
+    const size_t G = (size_t)e->G, GD = G * depth;
+    // staging: action i32[G][depth] | n i32[G][depth] | w f32[G][depth] | len i32[G]
+    if (e->readout.reserve(GD * 12 + G * 4)) TG_FAIL(ctx, TG_ERR_HIP, "hipMalloc failed");
+    int32_t* d_act = (int32_t*)e->readout.p; int32_t* d_n = d_act + GD;
+    float* d_w = (float*)(d_n + GD); int32_t* d_len = (int32_t*)(d_w + GD);
+    TG_LAUNCH(ctx, k_tree_pv, e->G, e->dev, depth, action ? d_act : nullptr, n ? d_n : nullptr, w ? d_w : nullptr, len ? d_len : nullptr);
+    if (action) TG_HIP(ctx, hipMemcpyAsync(action, d_act, sizeof(int32_t) * GD, hipMemcpyDeviceToHost, ctx->stream));
+    if (n) TG_HIP(ctx, hipMemcpyAsync(n, d_n, sizeof(int32_t) * GD, hipMemcpyDeviceToHost, ctx->stream));
+    if (w) TG_HIP(ctx, hipMemcpyAsync(w, d_w, sizeof(float) * GD, hipMemcpyDeviceToHost, ctx->stream));
+    if (len) TG_HIP(ctx, hipMemcpyAsync(len, d_len, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
     TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return TG_OK;
 }

@@ -112,7 +112,8 @@ class SelfPlayEngine:
         self.ctx = _lib.Context(cfg)
         self.G, self.S, self.P, self.A, self.C = n_games, board_size, board_size ** 2, board_size ** 2 + 1, encode_dim
         self.num_simulation = num_simulation
-        self.evaluator = evaluator            # None -> network on the GPU; callable(obs)->(policy, value) -> injected
+        self.path_capacity = (max_step + 2 + 63) // 64 * 64      # SearchCfg::maxd: the deepest line principal_variation can return
+        self.evaluator = evaluator           # None -> network on the GPU; callable(obs)->(policy, value) -> injected
         self.finished = np.zeros(n_games, bool)      # slots that take no part in the next search (game over, parked, in error)
         self.errored = np.zeros(n_games, bool)       # slots parked by a tree-arena overflow (restart them with reset(mask))
         self.device = device
@@ -208,6 +209,32 @@ class SelfPlayEngine:
         vis = np.zeros((self.G, self.A), np.int32); st = np.zeros(self.G, np.int32)
         self.ctx.call("tg_sp_root_info", _ptr(vis), None, None, _ptr(st), None)
         return vis, st
+
+    # ---- tree read-out (analysis; reads only, legal between any two engine calls) ------------------------------------------
+    CHILD_PRESENT, CHILD_OPEN, CHILD_PRIOR32, CHILD_WIN, CHILD_LOSS = 1, 2, 4, 8, 16        # TG_CHILD_* bits of "flags"
+    ROOT_OK, ROOT_PARKED, ROOT_UNEVALUATED, ROOT_TERMINAL, ROOT_ERROR = 0, 1, 2, 3, 4        # TG_ROOT_* values of "status"
+
+    def root_children(self):
+        """tg_sp_root_children: the Node_V fields (self_play.py:51-63) of every root child as dense [G, A] arrays -- "n", "pending",
+        "w", "var" (float32 as stored), "prior" (float64), "flags" (CHILD_* bits; 0 = the action is not legal at the root) -- and
+        per game "root_n", "root_pending", "root_w", "root_var" and "status" (ROOT_*)."""
+        G, A = self.G, self.A
+        r = dict(n=np.zeros((G, A), np.int32), pending=np.zeros((G, A), np.int32), w=np.zeros((G, A), np.float32),
+                 var=np.zeros((G, A), np.float32), prior=np.zeros((G, A), np.float64), flags=np.zeros((G, A), np.uint8),
+                 root_n=np.zeros(G, np.int32), root_pending=np.zeros(G, np.int32), root_w=np.zeros(G, np.float32),
+                 root_var=np.zeros(G, np.float32), status=np.zeros(G, np.uint8))
+        self.ctx.call("tg_sp_root_children", *[_ptr(a) for a in r.values()])
+        return r
+
+    def principal_variation(self, depth=16):
+        """tg_sp_pv: per game the line of most-visited children (ties: lowest action) from the root, at most `depth` moves.
+        Returns (actions [G, depth] padded with -1, visits [G, depth], w [G, depth], lengths [G])."""
+        depth = int(depth)
+        shape = (self.G, max(depth, 0))
+        act = np.full(shape, -1, np.int32); n = np.zeros(shape, np.int32); w = np.zeros(shape, np.float32)
+        ln = np.zeros(self.G, np.int32)
+        self.ctx.call("tg_sp_pv", depth, _ptr(act), _ptr(n), _ptr(w), _ptr(ln))
+        return act, n, w, ln
 
     def choose_moves(self, visits, steps, selfplay=True):
         """self_play.py:666-683 for every live game, in NumPy float64 with the reference's own operations:
