@@ -9,7 +9,13 @@ the batch are shown: `mem.sample(B)` (host arrays, fed through the reference's n
 tower's state_dict layout; its weights go back into the engine through the same `set_weights` the reference actor calls.
 
     python examples/selfplay_to_trainer.py            # needs an MI355X; ~10 s
+    python examples/selfplay_to_trainer.py --checkpoint /tmp/gen.ckpt --every 5     # games in flight + replay store saved every 5 moves
+    python examples/selfplay_to_trainer.py --resume /tmp/gen.ckpt                   # pick the generation up where the file left it
+
+A checkpoint is two files: PATH (BatchedSelfPlay.save_checkpoint: the games in flight) and PATH.replay (DeviceReplayMemory.save).
+Weights are not part of either; the example rebuilds them from its fixed torch seed, a real job loads its own.
 """
+import argparse
 import os
 import sys
 
@@ -80,7 +86,7 @@ def loss_fn(net, state, pi, z, own_z):                            # trainer.py:5
     return value_loss + 0.75 * own_loss + 1.15 * act_policy_loss + 0.02 * entropy_loss
 
 
-def main(games=64, sims=32, max_step=20, filters=32, blocks=2, batch=256, steps=3):
+def main(games=64, sims=32, max_step=20, filters=32, blocks=2, batch=256, steps=3, checkpoint=None, every=0, resume=None):
     dev = torch.device("cuda", 0)
     cfg = Config(num_simulation=sims, max_step=max_step, num_features=filters, num_blocks=blocks, buffer_size=8 * 65536)
     torch.manual_seed(0)
@@ -88,10 +94,23 @@ def main(games=64, sims=32, max_step=20, filters=32, blocks=2, batch=256, steps=
     sp = BatchedSelfPlay(cfg, games)
     sp.set_weights({k: v.detach().cpu() for k, v in net.eval().state_dict().items()})      # model.get_weights() -> actor (model.py:23-27)
     mem = DeviceReplayMemory(cfg, capacity_positions=65536)
+    if resume:                                                   # same config, same weights: the games continue move for move
+        sp.load_checkpoint(resume)
+        mem.load(resume + ".replay")
+        print("resumed:", sp.games_finished, "games finished,", mem.info()["entries"], "replay entries")
+    moves = 0
     while sp.games_finished < games:                             # one generation of complete games
         h = sp.advance(device=True)
         if h is not None:
             mem.append_harvest(h)                                # HBM -> HBM
+        moves += 1
+        if checkpoint and every > 0 and moves % every == 0:      # between two advance() calls: a move boundary
+            # the store first: a resume never finds games whose finished predecessors are missing from the store.  The opposite
+            # hazard remains: a crash between the two files leaves a NEW store next to the OLD games, and a resume then finishes
+            # and appends again the games that ended in between (duplicates, nothing lost) -- a job that minds writes both under
+            # one generation number and resumes from the newest complete pair
+            mem.save(checkpoint + ".replay")
+            sp.save_checkpoint(checkpoint)
     print("self-play:", sp.games_finished, "games,", mem.info()["entries"], "replay entries (8 per position)")
     opt = torch.optim.Adam(net.parameters(), lr=1e-3)
     net.train()
@@ -114,4 +133,9 @@ def main(games=64, sims=32, max_step=20, filters=32, blocks=2, batch=256, steps=
 
 
 if __name__ == "__main__":
-    main()
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--checkpoint", default=None, metavar="PATH", help="write PATH and PATH.replay every --every moves")
+    ap.add_argument("--every", type=int, default=10, metavar="N")
+    ap.add_argument("--resume", default=None, metavar="PATH", help="continue from a checkpoint written by --checkpoint")
+    a = ap.parse_args()
+    main(checkpoint=a.checkpoint, every=a.every, resume=a.resume)

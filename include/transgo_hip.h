@@ -249,6 +249,28 @@ int tg_sp_final(tg_ctx* ctx, float* score /*[G]*/, float* terr /*[G][S*S]*/, int
 int tg_sp_stats(tg_ctx* ctx, uint64_t* sims, uint64_t* evals, uint64_t* depth_sum, uint64_t* tie_draws, int32_t* errors,
                 int32_t* max_slots);
 
+/* ---- checkpoint and resume: the whole engine as one flat byte buffer ------------------------------------------------------------
+ * The reference checkpoints its replay buffer (replay_buffer.py:49-87, transgo.py:225-250); its games in flight are lost with the
+ * process.  Here the population itself can be put down and picked up again, or forked (one snapshot restored into two contexts).
+ * A snapshot is legal at a MOVE BOUNDARY only: no evaluation batch pending and no game inside a search -- between tg_sp_play +
+ * tg_sp_expand_roots (or tg_sp_reset + tg_sp_expand_roots) and the next tg_sp_begin_move; anywhere else TG_ERR_STATE.  It holds
+ * every game's control record, tree, RNG stream, move record and counters, the tree pool's ring and statistics, and the
+ * finished games tg_sp_harvest has not taken yet; the tree pool is PACKED (the chunks trees own, not the provisioned pool), so a
+ * snapshot costs what is in use.  Network weights are not part of it (load them as before; a restore into a context without
+ * weights succeeds and the next search reports "no network weights loaded"), nor is a pending background refresh.
+ * device_mem != 0: the buffer is in this GPU's memory (16-byte aligned; fork / migrate without a host bounce).  With a HOST buffer
+ * the snapshot is packed in (or scattered from) a staging buffer of its size in HBM, which the context then keeps for the next
+ * checkpoint until tg_destroy (371 MiB at 4096 boards / 400 simulations); the device path allocates nothing of that size.
+ * tg_sp_snapshot_size: the bytes tg_sp_snapshot would write now.  tg_sp_snapshot: cap = room in `out`, written = bytes used.
+ * tg_sp_restore takes a snapshot into a context created with the same board_size, encode_dim, n_games, parallel_readouts,
+ * max_step, komi, wu_loss, c_puct1/2, record_games, arena_slots and pool_slots (num_simulation, device and the network may
+ * differ); a mismatch is refused with a message that names the field and both values.  A truncated buffer, a wrong magic or
+ * version, a section past the end, a chunk id outside the pool or listed twice are refused too -- all BEFORE anything in the
+ * context is overwritten: a refused restore leaves the context as it was. */
+int tg_sp_snapshot_size(tg_ctx* ctx, uint64_t* bytes);
+int tg_sp_snapshot(tg_ctx* ctx, void* out, uint64_t cap, int device_mem, uint64_t* written);
+int tg_sp_restore(tg_ctx* ctx, const void* in, uint64_t bytes, int device_mem);
+
 /* ---- network -------------------------------------------------------------------------------------------------------------
  * Replaces TransGoNetwork.set_weights / main_prediction (model.py:17-27).  The blob is the BatchNorm-folded, kernel-layout
  * packing of the model's state_dict produced by transgo_amd/model.py:pack_weights (layout documented there and in
@@ -317,6 +339,16 @@ int tg_replay_append_dev(tg_replay* rp, const uint32_t* obs_bits, const int32_t*
 int tg_replay_info(const tg_replay* rp, long long* entries, long long* index, int* full);
 int tg_replay_sample(tg_replay* rp, const long long* entry /*[B]*/, int B, float* state /*[B][C][S][S]*/, float* pi /*[B][A]*/,
                      float* z /*[B]*/, float* own /*[B][S*S]*/, int device_out);
+/* Checkpoint of the store (save / load of replay_buffer.py:49-87).  tg_replay_export copies the slots first_position ..
+ * first_position + n - 1 out in STORAGE order (slot p holds the position appended p-th modulo the capacity), to host arrays of
+ * tg_replay_append's layouts; first_position + n may not exceed the positions held (entries / 8).  tg_replay_import writes slots
+ * 0 .. n_held - 1 verbatim and sets the append counter, so the ring position and the mapping from entry e to (position,
+ * symmetry) are those of the exported store.  Only appended mod capacity and whether appended >= capacity are observable
+ * (tg_replay_info), so a saver may pass the counter normalised to capacity + ring position for a full store; refused (TG_ERR_ARG) when n_held exceeds the capacity or differs from
+ * min(appended, capacity). */
+int tg_replay_export(tg_replay* rp, long long first_position, int n, uint32_t* obs_bits, int32_t* counts, float* z, int8_t* own);
+int tg_replay_import(tg_replay* rp, const uint32_t* obs_bits, const int32_t* counts, const float* z, const int8_t* own, int n_held,
+                     long long appended);
 
 /* ---- 3. host-only NumPy-legacy MT19937 helpers ------------------------------------------------------------------------
  * Same stream as np.random.RandomState: key/pos are get_state()[1] / get_state()[2].  No GPU needed. */

@@ -91,6 +91,11 @@ SIGNATURES = {
     "tg_replay_append_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "tg_replay_info": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int)]),
     "tg_replay_sample": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int]),
+    "tg_replay_export": (ctypes.c_int, [_vp, ctypes.c_longlong, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "tg_replay_import": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_longlong]),
+    "tg_sp_snapshot_size": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
+    "tg_sp_snapshot": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]),
+    "tg_sp_restore": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_int]),
     "tg_host_mt_seed": (None, [ctypes.POINTER(TgMt19937), ctypes.c_uint32]),
     "tg_host_mt_next32": (ctypes.c_uint32, [ctypes.POINTER(TgMt19937)]),
     "tg_host_mt_random_sample": (ctypes.c_double, [ctypes.POINTER(TgMt19937)]),

@@ -67,6 +67,7 @@ struct Engine {
     DevBuf hv_obs, hv_cnt, hv_z, hv_own, hv_pl, hv_game;   // harvest staging when the caller wants host arrays
     DevBuf obs_f32;                  // float planes of the pending batch, only materialised for tg_sp_batch_obs (tests, host evaluators)
     DevBuf readout;                  // staging of tg_sp_root_children / tg_sp_pv, allocated by the first such call
+    DevBuf snap_tab, snap_stage;     // snapshot.hip: scan offsets, and the packed snapshot on its way to / from a host buffer
     std::vector<double> h_noise;
     std::vector<int32_t> h_nchild;
     Net* net = nullptr;

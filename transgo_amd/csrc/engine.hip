@@ -1164,7 +1164,7 @@ void tg_engine_destroy(tg_ctx* ctx) {
                     e->d_fin, e->dev.hist_obs, e->dev.hist_cnt, e->dev.hist_pl};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->h_rng) (void)hipHostFree(e->h_rng);
-    e->obs_f32.release(); e->readout.release(); e->hv_obs.release(); e->hv_cnt.release(); e->hv_z.release(); e->hv_own.release(); e->hv_pl.release(); e->hv_game.release();
+    e->obs_f32.release(); e->readout.release(); e->snap_tab.release(); e->snap_stage.release(); e->hv_obs.release(); e->hv_cnt.release(); e->hv_z.release(); e->hv_own.release(); e->hv_pl.release(); e->hv_game.release();
     for (hipEvent_t ev : e->tev) (void)hipEventDestroy(ev);
     tg_net_destroy(ctx);
     delete e;

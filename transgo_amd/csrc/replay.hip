@@ -152,6 +152,48 @@ int tg_replay_info(const tg_replay* h, long long* entries, long long* index, int
     return TG_OK;
 }
 
+// Checkpoint of the store (the reference's save / load, replay_buffer.py:49-87).  Slots travel in STORAGE order with the
+// append counter, so the ring position -- and with it the mapping from entry e to (position, symmetry) -- is unchanged by a
+// save + load.  Export copies slots [first_position, first_position + n) to host arrays (callers go through a large store in
+// bounded pieces); import writes slots [0, n_held) verbatim and sets the counter.
+int tg_replay_export(tg_replay* h, long long first_position, int n, uint32_t* obs_bits, int32_t* counts, float* z, int8_t* own) {
+    if (!h || first_position < 0 || n < 0) return TG_ERR_ARG;
+    tg_ctx* ctx = h->ctx; Replay& r = h->r;
+    const long long held = r.appended < r.cap ? r.appended : r.cap;
+    if (first_position + n > held) TG_FAIL(ctx, TG_ERR_ARG, "tg_replay_export: slots beyond what the store holds");
+    if (n == 0) return TG_OK;
+    if (!obs_bits || !counts || !z || !own) return TG_ERR_ARG;
+    TG_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    const size_t at = (size_t)first_position;
+    TG_HIP(ctx, hipMemcpyAsync(obs_bits, r.obs + at * r.obs_words, sizeof(uint32_t) * (size_t)n * r.obs_words, hipMemcpyDeviceToHost, ctx->stream));
+    TG_HIP(ctx, hipMemcpyAsync(counts, r.counts + at * r.A, sizeof(int32_t) * (size_t)n * r.A, hipMemcpyDeviceToHost, ctx->stream));
+    TG_HIP(ctx, hipMemcpyAsync(z, r.z + at, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    TG_HIP(ctx, hipMemcpyAsync(own, r.own + at * r.P, (size_t)n * r.P, hipMemcpyDeviceToHost, ctx->stream));
+    TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return TG_OK;
+}
+
+int tg_replay_import(tg_replay* h, const uint32_t* obs_bits, const int32_t* counts, const float* z, const int8_t* own, int n_held,
+                     long long appended) {
+    if (!h) return TG_ERR_ARG;
+    tg_ctx* ctx = h->ctx; Replay& r = h->r;
+    if (n_held < 0 || n_held > r.cap) TG_FAIL(ctx, TG_ERR_ARG, "tg_replay_import: more positions than the store's capacity");
+    if (appended < 0 || (long long)n_held != (appended < r.cap ? appended : (long long)r.cap))
+        TG_FAIL(ctx, TG_ERR_ARG, "tg_replay_import: the append counter does not match the number of positions held");
+    if (n_held > 0 && (!obs_bits || !counts || !z || !own)) return TG_ERR_ARG;
+    TG_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    if (n_held > 0) {
+        const size_t n = (size_t)n_held;
+        TG_HIP(ctx, hipMemcpyAsync(r.obs, obs_bits, sizeof(uint32_t) * n * r.obs_words, hipMemcpyHostToDevice, ctx->stream));
+        TG_HIP(ctx, hipMemcpyAsync(r.counts, counts, sizeof(int32_t) * n * r.A, hipMemcpyHostToDevice, ctx->stream));
+        TG_HIP(ctx, hipMemcpyAsync(r.z, z, sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream));
+        TG_HIP(ctx, hipMemcpyAsync(r.own, own, n * r.P, hipMemcpyHostToDevice, ctx->stream));
+        TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    r.appended = appended;
+    return TG_OK;
+}
+
 // Materialise entries entry[0..B) (index into the reference's ring of augmented tuples: position = e/8, symmetry = e%8).
 // Outputs are float32; `device_out` != 0: the four pointers are device memory (e.g. torch tensors on this GPU), else host.
 int tg_replay_sample(tg_replay* h, const long long* entry, int B, float* state, float* pi, float* z, float* own, int device_out) {

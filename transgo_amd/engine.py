@@ -292,6 +292,54 @@ class SelfPlayEngine:
             buf[:hdr].copy_(torch.from_numpy(host.buf))
         return h
 
+    # ---- checkpoint and resume ------------------------------------------------------------------------------------------------
+    def snapshot(self, device=False):
+        """tg_sp_snapshot: the whole engine -- every game's tree, control record, RNG stream and move record, the tree pool's ring
+        and statistics, the counters, finished games not harvested yet -- as one flat uint8 buffer: a NumPy array, or with
+        device=True a torch tensor in this GPU's memory (fork / migrate without a host bounce).  Legal at a move boundary only
+        (between play() / reset() and the next search()).  The tree pool is packed: the buffer costs what the trees use, not what
+        the pool was provisioned with.  Network weights are not part of it.  (Two library calls: the size first, because the buffer
+        is allocated here; each runs the small scan kernel and one stream sync -- tens of microseconds next to the copy.  A host
+        snapshot leaves a staging buffer of its size in HBM with the context, for the next one.)"""
+        n = ctypes.c_uint64()
+        self.ctx.call("tg_sp_snapshot_size", ctypes.byref(n))
+        w = ctypes.c_uint64()
+        if device:
+            import torch
+            buf = torch.empty(n.value, dtype=torch.uint8, device=torch.device("cuda", self.device))
+            self.ctx.call("tg_sp_snapshot", ctypes.c_void_p(buf.data_ptr()), n.value, 1, ctypes.byref(w))
+        else:
+            buf = np.empty(n.value, np.uint8)
+            self.ctx.call("tg_sp_snapshot", _ptr(buf), n.value, 0, ctypes.byref(w))
+        return buf[:w.value]
+
+    def restore(self, buf):
+        """tg_sp_restore: take a snapshot() back -- into this engine or into another one created with the same geometry (board,
+        n_games, parallel_readouts, max_step, komi, search constants, record_games, arena_slots, pool_slots; num_simulation and the
+        device may differ) -- and with it `finished` / `errored`.  A damaged or mismatched buffer raises and leaves the engine as
+        it was.  Weights are the caller's to load, before or after."""
+        from . import snapshot as _snap
+        if isinstance(buf, (bytes, bytearray, memoryview)):
+            buf = np.frombuffer(buf, np.uint8)
+        on_gpu = not isinstance(buf, np.ndarray) and buf.is_cuda
+        if not isinstance(buf, np.ndarray) and not on_gpu:
+            buf = buf.numpy()
+        if on_gpu:
+            if buf.device.index != self.device:
+                raise ValueError(f"the snapshot tensor lives on GPU {buf.device.index}, this engine on GPU {self.device}: move it with "
+                                 f".to('cuda:{self.device}') first (tg_sp_restore reads device buffers of its own GPU only)")
+            assert buf.dtype.itemsize == 1 and buf.is_contiguous()
+            self.ctx.call("tg_sp_restore", ctypes.c_void_p(buf.data_ptr()), buf.numel(), 1)
+            hdr = _snap.parse_header(buf[:_snap.HEADER_BYTES].cpu().numpy())
+            off, size = hdr["sections"]["game_ctl"]
+            ctl = buf[off:off + size].cpu().numpy().view(_snap.GAME_CTL)
+        else:
+            buf = np.ascontiguousarray(buf, np.uint8)
+            self.ctx.call("tg_sp_restore", _ptr(buf), buf.size, 0)
+            hdr = _snap.parse_header(buf)
+            ctl = _snap.section(buf, hdr, "game_ctl", _snap.GAME_CTL)
+        self.finished, self.errored = _snap.game_flags(ctl)
+
     def final(self):
         score = np.zeros(self.G, np.float32); terr = np.zeros((self.G, self.P), np.float32); win = np.zeros(self.G, np.int32)
         self.ctx.call("tg_sp_final", _ptr(score), _ptr(terr), _ptr(win))

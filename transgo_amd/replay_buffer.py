@@ -129,6 +129,61 @@ class DeviceReplayMemory:
         self.ctx.lib.tg_replay_info(self.h, self._ct.byref(e), self._ct.byref(i), self._ct.byref(f))
         return {"capacity": self.capacity * 8, "index": i.value, "full": bool(f.value), "entries": e.value}
 
+    # ---- save / load (replay_buffer.py:49-87 for the device store) -----------------------------------------------------------
+    SAVE_PIECE = 1 << 16                                             # positions per tg_replay_export call
+
+    def save(self, path):
+        """The store as one file: magic, (S, C, capacity, appended) as int64, then obs_bits / counts / z / own of the positions held,
+        in storage order -- so a load() keeps the ring position and every entry index means the same sample.  `appended` is the
+        append counter NORMALISED: positions held while the store is not full, capacity + ring position once it is (the library
+        reports the counter only as ring position and `full`, and nothing else of it is observable).  Exported in pieces of
+        SAVE_PIECE positions: a large store needs no second copy in host memory.  Written under a temporary name, then moved."""
+        import os
+        from . import snapshot
+        info = self.info()
+        held = info["entries"] // 8
+        appended = held if not info["full"] else self.capacity + info["index"] // 8     # same ring position, same `full`
+        sec, _ = snapshot.replay_layout(self.S, self.C, held)
+        p = lambda a: a.ctypes.data_as(self._ct.c_void_p)
+        tmp = f"{path}.tmp.{os.getpid()}"
+        try:
+            with open(tmp, "wb") as f:
+                f.write(snapshot.REPLAY_MAGIC)
+                f.write(np.array([self.S, self.C, self.capacity, appended], np.int64).tobytes())
+                for at in range(0, held, self.SAVE_PIECE):          # each piece goes to its place in each of the four arrays
+                    n = min(self.SAVE_PIECE, held - at)
+                    arr = {k: np.empty((n,) + sec[k][2][1:], sec[k][1]) for k in sec}
+                    self._lib.check(self.ctx.lib, self.ctx.h, self.ctx.lib.tg_replay_export(
+                        self.h, at, n, p(arr["obs_bits"]), p(arr["counts"]), p(arr["z"]), p(arr["own"])))
+                    for k, (o, dt, shape) in sec.items():
+                        f.seek(o + at * int(np.prod(shape[1:])) * dt.itemsize)
+                        f.write(arr[k].tobytes())
+                f.flush()
+                os.fsync(f.fileno())
+            os.replace(tmp, path)
+        except BaseException:
+            try:
+                os.unlink(tmp)
+            except OSError:
+                pass
+            raise
+
+    def load(self, path):
+        """Take a save() back: the file must come from a store of the same board size, planes and capacity (ValueError otherwise,
+        and for a damaged file).  The arrays are read through a memory map, so the file's pages are the only host copy."""
+        from . import snapshot
+        S, C, cap, appended, held, sec = snapshot.read_replay_header(path)
+        if (S, C, cap) != (self.S, self.C, self.capacity):
+            raise ValueError(f"replay store file of board {S}, {C} planes, capacity {cap}; this store has {self.S}, {self.C}, {self.capacity}")
+        if held:
+            mm = np.memmap(path, np.uint8, "r")
+            arr = {k: np.ascontiguousarray(mm[o:o + int(np.prod(shape)) * dt.itemsize]) for k, (o, dt, shape) in sec.items()}
+            p = lambda a: a.ctypes.data_as(self._ct.c_void_p)
+            args = [p(arr[k]) for k in ("obs_bits", "counts", "z", "own")]
+        else:
+            args = [None] * 4
+        self._lib.check(self.ctx.lib, self.ctx.h, self.ctx.lib.tg_replay_import(self.h, *args, held, appended))
+
     def sample_entries(self, entries):
         entries = np.ascontiguousarray(entries, np.int64)
         B = len(entries)

@@ -205,6 +205,69 @@ class BatchedSelfPlay:
             self.phase_s[k] = self.phase_s.get(k, 0.0) + v                        # wall-clock shares of a step (bench.py reports them)
         return h
 
+    # ---- checkpoint and resume (the games in flight; the reference checkpoints its buffer only, transgo.py:225-250) --------------
+    def checkpoint_state(self):
+        """The worker's own bookkeeping as plain JSON data (the engine's share is SelfPlayEngine.snapshot)."""
+        ls = lambda a: None if a is None else [int(x) for x in a]
+        return {"n_games": self.G, "board_size": self.S, "arch": self.arch.code,
+                "games_started": ls(self.games_started), "seeds": ls(self.seeds), "moves_played": int(self.moves_played),
+                "games_finished": int(self.games_finished), "games_dropped": int(self.games_dropped), "last_live": int(self.last_live),
+                "_started": bool(self._started), "_parked": ls(self._parked), "_start_at": ls(getattr(self, "_start_at", None)),
+                "_step_no": int(getattr(self, "_step_no", 0)),
+                "finished": ls(self.engine.finished), "errored": ls(self.engine.errored)}
+
+    def _check_part(self, state, snap):
+        """What can be told on the host without touching the engine: the worker state fits this worker, and the snapshot's header
+        is whole and describes this worker's games."""
+        from . import snapshot
+        if state.get("n_games") != self.G or state.get("board_size") != self.S:
+            raise ValueError(f"checkpoint of {state.get('n_games')} games at board size {state.get('board_size')}, "
+                             f"this worker runs {self.G} at {self.S}")
+        if state.get("arch") != self.arch.code:
+            raise ValueError(f"checkpoint taken with network layout {state.get('arch')!r}, this worker is configured for {self.arch.code!r}")
+        for k in ("games_started", "seeds", "finished", "errored"):
+            if not isinstance(state.get(k), list) or len(state[k]) != self.G:
+                raise ValueError(f"checkpoint header: {k} does not list {self.G} games")
+        hdr = snapshot.parse_header(snap)
+        snapshot.check_length(hdr, len(snap))
+        if (hdr["n_games"], hdr["board_size"]) != (self.G, self.S):
+            raise ValueError(f"engine snapshot of {hdr['n_games']} games at board size {hdr['board_size']}, this worker runs {self.G} at {self.S}")
+
+    def _restore_part(self, state, snap):
+        self._check_part(state, snap)
+        self.engine.restore(snap)                                      # refuses a mismatched geometry before it changes anything
+        self.games_started = np.asarray(state["games_started"], np.int64)
+        self.seeds = np.asarray(state["seeds"], np.uint32)
+        self.moves_played, self.games_finished = int(state["moves_played"]), int(state["games_finished"])
+        self.games_dropped, self.last_live = int(state["games_dropped"]), int(state["last_live"])
+        self._started = bool(state["_started"])
+        self._parked = None if state["_parked"] is None else np.asarray(state["_parked"], bool)
+        if state["_start_at"] is not None:
+            self._start_at = np.asarray(state["_start_at"], np.int64)
+        self._step_no = int(state["_step_no"])
+        self.engine.finished = np.asarray(state["finished"], bool)
+        self.engine.errored = np.asarray(state["errored"], bool)
+
+    def save_checkpoint(self, path):
+        """Everything needed to continue these games in another process, in ONE file: the engine snapshot (trees, RNG streams, move
+        records, pool state, counters) behind a JSON header with this worker's own counters (games_started, seeds, moves_played,
+        games_finished, games_dropped, the stagger bookkeeping, the network layout code).  Legal between two advance() calls.  The
+        file is written under a temporary name and moved into place, so `path` never holds a partial checkpoint.  Data only: no
+        pickle.  Network weights are NOT saved -- load them as before; `seed_fn` is not serialisable either: pass the same one to
+        the worker that loads the checkpoint, or games started after the resume get different seeds."""
+        from . import snapshot
+        snapshot.write_checkpoint(path, [(self.checkpoint_state(), self.engine.snapshot())])
+
+    def load_checkpoint(self, path):
+        """Continue from save_checkpoint's file: into a worker built with the same config, n_games, arena_slots / pool_slots and
+        seed_fn (num_simulation and the device may differ).  A damaged file raises ValueError, a mismatched engine TransgoError;
+        either leaves the worker as it was.  Weights are loaded by the caller, before or after."""
+        from . import snapshot
+        parts = snapshot.read_checkpoint(path)
+        if len(parts) != 1:
+            raise ValueError(f"checkpoint of {len(parts)} groups, this worker is a single engine")
+        self._restore_part(*parts[0])
+
     def step(self, selfplay=True):
         """advance() with the finished games unpacked into GameRecord objects (host lists, as the reference keeps them)."""
         h = self.advance(selfplay)
@@ -308,6 +371,26 @@ class GroupedSelfPlay:
     def advance(self, selfplay=True, device=False, num_simulation=0):
         """One move of every game of every group; returns the groups' finished-game batches (records.Harvest or None), in group order."""
         return self._each(lambda p: p.advance(selfplay, device, num_simulation))
+
+    def save_checkpoint(self, path):
+        """BatchedSelfPlay.save_checkpoint for every group, as one file with one section per group (same rules: between two
+        advance() calls; no weights; written under a temporary name and moved into place)."""
+        from . import snapshot
+        snapshot.write_checkpoint(path, self._each(lambda p: (p.checkpoint_state(), p.engine.snapshot())))
+
+    def load_checkpoint(self, path):
+        """Into a worker with the same number of groups, config, n_games and arena_slots / pool_slots.  Every section's worker state
+        and snapshot header are checked against its group BEFORE the first group is restored (ValueError, nothing changed); what
+        only the library can refuse -- damage inside a snapshot's tables -- is met group by group, and such a refusal in group k
+        leaves groups 0 .. k-1 restored: build a new worker then."""
+        from . import snapshot
+        parts = snapshot.read_checkpoint(path)
+        if len(parts) != self.K:
+            raise ValueError(f"checkpoint of {len(parts)} groups, this worker has {self.K}")
+        for p, (state, snap) in zip(self.parts, parts):
+            p._check_part(state, snap)
+        for p, (state, snap) in zip(self.parts, parts):
+            p._restore_part(state, snap)
 
     @property
     def games_finished(self):
