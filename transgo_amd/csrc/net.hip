@@ -18,6 +18,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "conv_rows.h"
@@ -57,6 +59,7 @@ struct NetPath {
     size_t att_lds = 0;        // k_attention's dynamic LDS in bytes; 0: no attention, or its image does not fit
     int one_stream = 0;        // CHAIN_DMA: 1 between conv layers ONE f32 residual stream in the conv's row order, activated on load
                                // (default); 2 that stream, relu(bn1_next(.)) still written beside it; 0 (TG_ONE_STREAM=0) two tensors
+    bool conv_fp = true;       // CHAIN_DMA: k_conv3x3_sg with the shortened fixed part (FP); false (TG_CONV_FIXED_PART=0) the earlier prologue
 };
 
 struct Net {
@@ -417,7 +420,8 @@ __device__ __forceinline__ int swz64(int row) { return ((row >> 2) & 1) << 1; }
 // on-board (slice, tap, k) terms in the same order, so results are those of the full walk (x + w*0 = x).
 // Stage k = (16-channel slice k / nt, the (k % nt)-th on-board tap), nt = 4 / 6 / 9, so F/16 * nt stages -- always an even count.
 // A (weights): the stage's tile arrives by LDS-DMA from a stage-ordered copy of the weights ([slice*9+tap][cout][16]) into a
-// 4-slot ring (slot = k % 4), two stages per barrier, the next pair landing while this one is used; the LDS image is XOR-swizzled
+// 4-slot ring (slot = k % 4), two stages per barrier, the next pair landing while this one is used (the prologue: stages 0 and 1
+// in front of the first barrier, 2 and 3 behind it -- see FP below); the LDS image is XOR-swizzled
 // at the source (swz64) so ds_read_b128 fragments are conflict-free.  Stages per barrier at F = 128, measured on the row-ordered
 // kernel: 2: 138.5, 3: 131.6, 4: 127.1 TFLOP/s.  B (activations): every wave loads its own B fragments straight from L2 into
 // registers, a stage ahead; a tap is the wave-uniform shift of (dy*S + dx)*16 rows inside the board group.  Everything is at least
@@ -431,7 +435,28 @@ __device__ __forceinline__ int swz64(int row) { return ((row >> 2) & 1) << 1; }
 // in the activating kernel only) and 67 KB, two per CU.  Three tiles per wave
 // (192 boards, three workgroups per CU at F = 128), the better shape of the row-ordered kernel on full rounds, measured 4-7 %
 // slower here at 9x9 and 19x19: the walks differ in length, and four shorter waves per SIMD fill each other's gaps better.
-template <int S, int F, int EPI, bool SIN = false, bool SOUT = false>
+// The fixed part of a workgroup (FP, the default; FP = false is the prologue this replaced, kept as TG_CONV_FIXED_PART=0 for the A/B
+// and the bit-identity test -- every accumulation runs in the same order in both):
+//  * bias | s2 | t2 are fetched into registers FIRST and written to `par` behind everything the prologue issues, so their round
+//    trip runs beside the weight DMAs instead of in front of them (the first barrier publishes `par` as before);
+//  * the first barrier waits for the weight stages 0 and 1 only.  vmcnt retires in order, so what the first MFMA needs is issued
+//    first: stages 0 and 1, the B fragments of stage 0, then (EPI 1) the residual in the order of use, ct-major.  Stages 2 and 3
+//    go out behind the barrier and behind the first consumer of those loads (act_b, or an empty asm: the compiler waits for them
+//    there with vmcnt(0), the accumulators being live into a loop, and that wait must not include two more weight stages), and land
+//    during stage 0.  The stage-end vmcnt(0) covers them before the second barrier.  (In today's ISA the write of `par` still
+//    carries a compiler vmcnt(0), so the first barrier also sees the wave's B fragments and residual landed: DESIGN.md 8.8);
+//  * without the activation on load the hand-over b_cur = b_next goes through an empty asm at the END of the stage, as act_b does
+//    with VALU: the compiler cannot fold the copy into the next stage's MFMA operands, so its own vmcnt(0) for the fragments
+//    lands there, a stage after their load, and not in front of the next stage's first MFMA, a few instructions after the next load.
+// -DTG_CONV_STAMP (diagnostic build only, scripts/stamp_conv.py): phase stamps of wave 0 of six workgroups at 9x9 / F = 128.
+#ifdef TG_CONV_STAMP
+__device__ unsigned long long g_conv_stamp[2 * 6 * 8];                  // [EPI][interior, edge, corner of range 0 | of range 7][phase]
+#define TG_CSTAMP(i) do { __builtin_amdgcn_sched_barrier(0); if (cslot >= 0 && lane == 0) g_conv_stamp[cslot * 8 + (i)] = __builtin_readcyclecounter(); \
+                          __builtin_amdgcn_sched_barrier(0); } while (0)
+#else
+#define TG_CSTAMP(i) do { } while (0)
+#endif
+template <int S, int F, int EPI, bool SIN = false, bool SOUT = false, bool FP = true>
 __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const float* __restrict__ in, float* __restrict__ out,
                                                                        const float* __restrict__ res, const float* __restrict__ Ws,
                                                                        const float* __restrict__ bias, float* __restrict__ out2,
@@ -446,6 +471,10 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 15, kq = lane >> 4;
+#ifdef TG_CONV_STAMP
+    const unsigned long long t_entry = __builtin_readcyclecounter();
+    __builtin_amdgcn_sched_barrier(0);
+#endif
     // XCD-aware order: workgroup b runs on XCD b % 8, so XCD x takes the CONTIGUOUS run [x * tpx, (x + 1) * tpx) of the numbering
     // above -- the workgroups that read one board range's input share one L2
     const int tpx = ((int)gridDim.x + 7) >> 3;
@@ -456,7 +485,26 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
     const int p = conv_pos_of(bid - range * P, S);
     const int M = rows * P, Msm = conv_sg_rows(rows, P);
     constexpr bool ACT = EPI == 0 && SIN;                               // s2 / t2 are then the BN of `in`, applied as its fragments land
-    for (int i = tid; i < F; i += 256) { par[i] = bias[i]; par[F + i] = out2 || ACT ? s2[i] : 0.f; par[2 * F + i] = out2 || ACT ? t2[i] : 0.f; }
+#ifdef TG_CONV_STAMP
+    // range 0 runs in the first round of XCD 0, range 7 in the middle of its run of 15; conv_pos_of: interior, edge, corner positions
+    int cslot = -1;
+    if (S == 9 && F == 128 && (EPI == 0 || SOUT) && wave == 0 && (range == 0 || range == 7)) {
+        const int li = bid - range * P, I = S - 2;
+        const int cls = li == 0 ? 0 : li == I * I ? 1 : li == I * I + 4 * I ? 2 : -1;
+        if (cls >= 0) cslot = (EPI == 1 ? 6 : 0) + (range == 0 ? 0 : 3) + cls;
+    }
+    if (cslot >= 0 && lane == 0) g_conv_stamp[cslot * 8] = t_entry;
+#endif
+    static_assert(F <= 256, "one parameter triple per thread");
+    [[maybe_unused]] float pbias = 0.f, ps2 = 0.f, pt2 = 0.f;            // FP: this thread's element of bias | s2 | t2, in flight
+    [[maybe_unused]] const bool bn = out2 || ACT;                        // s2 / t2 are in use
+    if constexpr (FP) {                                                  // no branch around the loads (see TG_PAR_LANDED)
+        pbias = bias[tid & (F - 1)]; ps2 = (bn ? s2 : bias)[tid & (F - 1)]; pt2 = (bn ? t2 : bias)[tid & (F - 1)];
+        __builtin_amdgcn_sched_barrier(0);                               // issued here, ahead of the weight DMAs
+    } else {
+        for (int i = tid; i < F; i += 256) { par[i] = bias[i]; par[F + i] = out2 || ACT ? s2[i] : 0.f; par[2 * F + i] = out2 || ACT ? t2[i] : 0.f; }
+    }
+    TG_CSTAMP(1);
 
     // the workgroup's walk: nt on-board taps, packed 4 bits each; k / nt by a multiplication that is exact far beyond NSL * 9
     const unsigned mask = conv_tap_mask(p, S);
@@ -509,15 +557,25 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
 #pragma unroll
             for (int e = 0; e < 4; ++e) dst[t][e] = bn_relu_unpacked(b[t][e], bsc[e], bsh[e]);
     };
+    constexpr int NRES = EPI == 1 ? CT * NPT : 0;                        // residual loads per lane
+    // FP: the triple is older than the DMAs just waited for.  It is taken over by an asm that differs between the two paths, so that
+    // the compiler's wait for it stands on each path with that path's count (behind a merged tail it is vmcnt(0), and the barrier
+    // would wait for the residual too)
+#define TG_PAR_LANDED(PATH) do { if constexpr (FP) asm volatile("; bias, s2, t2 landed: " PATH : "+v"(pbias), "+v"(ps2), "+v"(pt2)); } while (0)
 #pragma unroll
-    for (int k = 0; k < D; ++k) dma_w(k);
+    for (int k = 0; k < (FP ? 2 : D); ++k) dma_w(k);
+    TG_CSTAMP(2);
     if (active) {
+        if constexpr (FP) {
+            load_b(b_cur, 0);
+            __builtin_amdgcn_sched_barrier(0);                           // ahead of the residual: the first MFMA needs them first
+        }
 #pragma unroll
-        for (int t = 0; t < NPT; ++t) {
+        for (int i = 0; i < CT * NPT; ++i) {                             // EPI 1: start from the residual (no loads behind the epilogue's stores)
+            const int ct = FP ? i / NPT : i % CT, t = FP ? i % NPT : i / CT;   // FP: in the order of use
             const int b = (grp0 + t) * 16 + j;
             [[maybe_unused]] const int m = b < rows ? b * P + p : M - 1;
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {                            // EPI 1: start from the residual (no loads behind the epilogue's stores)
+            {
                 acc[ct][t] = f32x4{0.f, 0.f, 0.f, 0.f};
                 // always issued (they are never stored for boards past the batch): the wait below counts them
                 if constexpr (EPI == 1 && SIN) {
@@ -530,22 +588,44 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
                 }
             }
         }
-        load_b(b_cur, 0);
+        if constexpr (!FP) load_b(b_cur, 0);
         // The barrier must see the weight DMAs of the first stages landed; the operations issued after them -- CT*NPT residual
         // loads, NPT B fragments -- are the wave's youngest and are waited for by the compiler, one by one, in front of the MFMA
         // that first needs each.
-        TG_VMCNT((EPI == 1 ? CT * NPT : 0) + NPT);
+        TG_VMCNT(NRES + NPT);
+        TG_PAR_LANDED("wave with boards");
     } else {
         TG_VMCNT(0);
+        TG_PAR_LANDED("wave without boards");
+    }
+#undef TG_PAR_LANDED
+    if constexpr (FP) {
+        if (tid < F) { par[tid] = pbias; par[F + tid] = bn ? ps2 : 0.f; par[2 * F + tid] = bn ? pt2 : 0.f; }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     TG_BARRIER();
+    TG_CSTAMP(3);
     if constexpr (ACT) {                                                 // `par` is published by the barrier above
         if (active) act_b(b_cur, b_cur);
         else {                                                           // written on both paths: the loop then waits for no load of b_cur
 #pragma unroll
             for (int t = 0; t < NPT; ++t) b_cur[t] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
+    }
+    if constexpr (FP) {
+        // Stages 2 and 3 go out behind the first consumer of everything loaded above: the compiler waits for those loads with
+        // vmcnt(0) (the accumulators are live into a loop), which must not include two more weight stages.
+        if (active) {
+#pragma unroll
+            for (int t = 0; t < NPT; ++t) {
+                if constexpr (!ACT) asm volatile("" : "+v"(b_cur[t]));
+                if constexpr (EPI == 1) {
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) asm volatile("" : "+v"(acc[ct][t]));
+                }
+            }
+        }
+        dma_w(2); dma_w(3);
     }
 
 #pragma unroll 1
@@ -568,13 +648,20 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
                         for (int t = 0; t < NPT; ++t)
                             acc[ct][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[s4], b_cur[t][s4], acc[ct][t], 0, 0, 0);
                     a_cur = a_next;
+#ifdef TG_CONV_STAMP
+                    if (ct == 0 && k == 0) TG_CSTAMP(4);                 // the first MFMAs have issued: their operands had landed
+#endif
                 }
                 if constexpr (ACT) {
                     __builtin_amdgcn_sched_barrier(0);                   // behind the stage's MFMAs: the fragments are a stage old here
                     act_b(b_cur, b_next);
                 } else {
+                    if constexpr (FP) __builtin_amdgcn_sched_barrier(0); // the same place for the fragments' wait
 #pragma unroll
-                    for (int t = 0; t < NPT; ++t) b_cur[t] = b_next[t];
+                    for (int t = 0; t < NPT; ++t) {
+                        if constexpr (FP) asm volatile("" : "+v"(b_next[t]));
+                        b_cur[t] = b_next[t];
+                    }
                 }
             }
             TG_VMCNT(0);                                                 // B fragments of stage k+1 (and any weight pieces): a stage old
@@ -582,6 +669,7 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
         TG_BARRIER();                                                    // the next pair has landed for everybody; this pair's slots are free
         if (k0 + 4 < nst) { dma_w(k0 + 4); dma_w(k0 + 5); }
     }
+    TG_CSTAMP(5);
     if (!active) return;
     int mrow[NPT], srow[NPT];
 #pragma unroll
@@ -591,6 +679,11 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
         srow[t] = conv_sg_row(b, p, P);
     }
     conv_epilogue<F, CT, NPT, (EPI == 1 ? 2 : EPI), EPI == 0 || SOUT, true>(acc, mrow, M, 0, kq, out, res, out2, par, srow, Msm);
+#ifdef TG_CONV_STAMP
+    TG_CSTAMP(6);                                                        // every store issued
+    TG_VMCNT(0);
+    TG_CSTAMP(7);                                                        // and written: the wave can end
+#endif
 }
 
 // fp16 activation tensors are CHUNK-MAJOR: [channels/32 slices][4 chunks of 8 channels][M rows][8 halfs].  A slab DMA piece (64 rows
@@ -2085,9 +2178,16 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
                 // one workgroup per (range of 128 boards, position), the count rounded up to the XCD-contiguous order's multiple of 8
                 const int grid_sd = ((rows + 127) / 128 * P + 7) / 8 * 8;
                 const bool onload = sin && one == 1;                 // conv1 reads the stream itself, else its activated copy
-                auto* k1 = onload ? &k_conv3x3_sg<S, F, 0, true> : &k_conv3x3_sg<S, F, 0>;
-                auto* k2 = sin ? (sout ? &k_conv3x3_sg<S, F, 1, true, true> : &k_conv3x3_sg<S, F, 1, true, false>)
-                               : (sout ? &k_conv3x3_sg<S, F, 1, false, true> : &k_conv3x3_sg<S, F, 1>);
+                auto pick = [&](auto fp) {                           // the two prologues of every variant (TG_CONV_FIXED_PART)
+                    constexpr bool FP = decltype(fp)::value;
+                    auto* c1 = onload ? &k_conv3x3_sg<S, F, 0, true, false, FP> : &k_conv3x3_sg<S, F, 0, false, false, FP>;
+                    auto* c2 = sin ? (sout ? &k_conv3x3_sg<S, F, 1, true, true, FP> : &k_conv3x3_sg<S, F, 1, true, false, FP>)
+                                   : (sout ? &k_conv3x3_sg<S, F, 1, false, true, FP> : &k_conv3x3_sg<S, F, 1, false, false, FP>);
+                    return std::make_pair(c1, c2);
+                };
+                const auto ks = n->path.conv_fp ? pick(std::true_type{}) : pick(std::false_type{});
+                auto* k1 = ks.first;
+                auto* k2 = ks.second;
                 { ProfScope ps(n, st, conv_flops);
                   hipLaunchKernelGGL(k1, dim3(grid_sd), dim3(256), 0, st, onload ? x : n->bufAct, n->bufH, nullptr, b.g1, b.c1.b, nullptr,
                                      onload ? b.s1 : nullptr, onload ? b.t1 : nullptr, rows); }
@@ -2413,6 +2513,8 @@ NetPath net_path(int S, int F, int prec, const std::string& trunk, bool pol) {
         p.chain = dma && atoi(dma) == 0 ? CHAIN_F32 : CHAIN_DMA;
         const char* one = getenv("TG_ONE_STREAM");                      // 0: two tensors (the A/B arm); 2: one stream, bufAct kept
         p.one_stream = one && one[0] >= '0' && one[0] <= '2' && !one[1] ? one[0] - '0' : 1;   // anything but one digit 0..2: the default
+        const char* fp = getenv("TG_CONV_FIXED_PART");                  // 0: k_conv3x3_sg's earlier prologue (the A/B arm)
+        p.conv_fp = !(fp && fp[0] == '0' && !fp[1]);
     }
     p.r16 = prec == 2;
     p.att_x3 = prec == 3 && any_att && F == 128 && S == 9;
@@ -2612,6 +2714,12 @@ int tg_net_load_poll(tg_ctx* ctx, int wait, int* pending) {
     return rc;
 }
 
+#ifdef TG_CONV_STAMP
+int tg_debug_conv_stamps(unsigned long long* out, int n) {
+    if (n > 96) n = 96;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_conv_stamp), sizeof(unsigned long long) * n) == hipSuccess ? 0 : -1;
+}
+#endif
 #ifdef TG_ATT_STAMP
 int tg_debug_att_stamps(unsigned long long* out, int n) {
     if (n > 32) n = 32;
@@ -2688,6 +2796,15 @@ int tg_net_stream_layout(tg_ctx* ctx, int* one_stream, int* act_copy) {
     const Net* n = ctx->eng->net;
     if (one_stream) *one_stream = n->path.chain == CHAIN_DMA ? n->path.one_stream : 0;
     if (act_copy) *act_copy = n->bufAct != nullptr;
+    return TG_OK;
+}
+
+// 1 where the loaded network's F->F convs run k_conv3x3_sg with the shortened fixed part, 0 with the earlier prologue
+// (TG_CONV_FIXED_PART=0) and on every other chain
+int tg_net_conv_fixed_part(tg_ctx* ctx, int* fixed_part) {
+    if (!ctx || !ctx->eng || !ctx->eng->net || !fixed_part) return TG_ERR_STATE;
+    const Net* n = ctx->eng->net;
+    *fixed_part = n->path.chain == CHAIN_DMA && n->path.conv_fp;
     return TG_OK;
 }
 
