@@ -15,7 +15,7 @@ from transgo_amd.engine import SelfPlayEngine                     # noqa: E402
 from transgo_amd.environment import GoEnv                         # noqa: E402
 
 
-def main(moves=("E5", "C3", "G7", "C7"), sims=200, filters=32, blocks=2, board_size=9):
+def main(moves=("E5", "C3", "G7", "C7"), sims=200, filters=32, blocks=2, board_size=9, playouts=0):
     env = GoEnv(board_size=board_size)
     state, _ = env.reset()
     names = {analysis.vertex(a, board_size): a for a in range(board_size ** 2 + 1)}
@@ -27,10 +27,12 @@ def main(moves=("E5", "C3", "G7", "C7"), sims=200, filters=32, blocks=2, board_s
     model.load_into(eng.ctx, model.random_weights(board_size, 10, filters, blocks, seed=3), board_size, 10, filters, blocks)
     eng.reset([0])                                                # seeds the stream the search's tie breaks draw from
     rec = analysis.analyse(eng, np.frombuffer(state, np.uint8).reshape(1, -1))[0]
-    print(analysis.format_analysis(rec, board_size, top=8))
+    # --playouts N: the network-free Monte-Carlo ownership / score estimate next to the search (N random games in one launch)
+    own = analysis.playout_ownership(env, np.frombuffer(state, np.uint8).reshape(1, -1), playouts=playouts)[0] if playouts else None
+    print(analysis.format_analysis(rec, board_size, top=8, ownership=own))
     eng.close()
     return rec
 
 
 if __name__ == "__main__":
-    main()
+    main(playouts=int(sys.argv[sys.argv.index("--playouts") + 1]) if "--playouts" in sys.argv else 0)

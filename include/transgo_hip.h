@@ -117,6 +117,26 @@ typedef struct tg_mt19937 {
     int32_t pos;
 } tg_mt19937;
 
+/* Uniformly random playouts, the whole game in ONE kernel launch (the reference plays them ply by ply on the host:
+ * test_trans.py:14-23 RandomBot, :60-95 evaluate2, over getLegalAction / getLegalNoEye, environment.py:121-129, :161-164).
+ * Candidate policies: */
+#define TG_ROLLOUT_NOEYE 0      /* getLegalNoEye without its trailing pass (go_env.cc:171-181): own true eyes are never filled */
+#define TG_ROLLOUT_LEGAL 1      /* the pass-filtered getLegalAction of environment.py:121-129: what RandomBot draws from */
+/* Per board i, with rs = np.random.RandomState at rng[i] (NumPy's legacy stream, not Python's `random`):
+ *     plies = 0
+ *     while not terminated(state) and plies < max_plies[i]:
+ *         pts = candidates(state)                     # ascending points, pass excluded
+ *         a = S*S if len(pts) == 0 else rs.choice(pts)    # a one-element choice makes NO draw
+ *         state, done = Step(state, a);  moves[i][plies] = a;  plies += 1
+ * out[i] = the last state, rng[i] = the stream behind the last draw, plies[i], done[i] = terminated (double pass or step_count >
+ * max_step, as tg_env_step reports it); moves i32[n][moves_cap] (may be NULL) holds -1 behind the last ply.  max_plies NULL = play
+ * every game to its end.  A board that arrives terminated, or whose budget is 0, comes back unchanged with plies 0 and its stream
+ * untouched.  TG_ERR_ARG: unknown policy, a negative budget, a stream position outside 0..624, `moves` with moves_cap smaller than
+ * the largest budget (or than max_step when max_plies is NULL).  in may equal out. */
+int tg_env_rollout(tg_ctx* ctx, const void* in, void* out, int n, tg_mt19937* rng /*[n], in and out*/,
+                   const int32_t* max_plies /*[n] or NULL*/, int policy, int32_t* plies /*[n]*/, uint8_t* done /*[n]*/,
+                   int32_t* moves /*[n][moves_cap] or NULL*/, int moves_cap);
+
 /* ---- 2. batched self-play engine (needs cfg.n_games > 0) -----------------------------------------------------------------
  * G games advance in lock step.  One move of every game is:
  *     tg_sp_begin_move -> { tg_sp_collect -> evaluate -> tg_sp_absorb } until no game is active

@@ -42,6 +42,7 @@ SIGNATURES = {
     "tg_env_step": (ctypes.c_int, [_vp, _vp, _vp, _i32p, ctypes.c_int, _u8p, _u8p]),
     "tg_env_query": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _u8p, _u8p, _f32p, _f32p, _f32p, _i32p, _i32p, _u8p]),
     "tg_env_show": (ctypes.c_int, [_vp, _vp]),
+    "tg_env_rollout": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _i32p, ctypes.c_int, _i32p, _u8p, _i32p, ctypes.c_int]),
     "tg_sp_reset": (ctypes.c_int, [_vp, _vp, _vp]),
     "tg_sp_reset_from": (ctypes.c_int, [_vp, _vp, _vp]),
     "tg_sp_root_states": (ctypes.c_int, [_vp, _vp]),

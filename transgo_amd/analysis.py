@@ -60,10 +60,49 @@ def analyse(engine, states, num_simulation=0, depth=16):
     return out
 
 
-def format_analysis(record, board_size, top=5):
+def playout_ownership(env, states, playouts=64, seed=0):
+    """The network-free Monte-Carlo estimate of every position of `states` ([N, state_size] blobs of `env`, a
+    transgo_amd.environment.GoEnv): `playouts` uniformly random no-eye games per position, all N * playouts of them in ONE
+    kernel launch (GoEnv.rollout_batch; game k of position i is seeded seed + i * playouts + k), each scored by Tromp-Taylor.
+    One dict per position:
+      territory  float64[P]  mean owner of each point over the games, +1 black / -1 white (an integer sum / playouts)
+      score      float       mean of getScore (Tromp-Taylor - komi) over the games
+      black_win  float       share of the games black wins (score > 0, environment.py:118-119)
+      playouts   int"""
+    states = np.ascontiguousarray(states, np.uint8)
+    if states.ndim != 2:
+        raise ValueError("states must be [N, state_size]")
+    N, K = states.shape[0], int(playouts)
+    if K <= 0:
+        raise ValueError("playouts must be positive")
+    if N == 0:
+        return []
+    seeds = (int(seed) + np.arange(N * K, dtype=np.int64)) % (2 ** 32)
+    end = env.rollout_batch(np.repeat(states, K, axis=0), seeds=seeds)["states"]
+    q = env.query_batch(end, score=True, terr=True)
+    terr = q["terr"].astype(np.int64).reshape(N, K, -1)               # exactly -1 / 0 / +1
+    score = q["score"].astype(np.float64).reshape(N, K)
+    return [dict(territory=terr[i].sum(0) / K, score=float(score[i].sum() / K), black_win=float((score[i] > 0).sum() / K),
+                 playouts=K) for i in range(N)]
+
+
+def format_ownership(record, board_size):
+    """The territory map of one `playout_ownership` record as a board of percentages (+100 black ... -100 white), with the mean
+    score and black's win rate on top."""
+    S = int(board_size)
+    t = np.asarray(record["territory"]).reshape(S, S)
+    lines = [f"playouts {int(record['playouts'])}   mean score {record['score']:+.2f}   black wins {100 * record['black_win']:.1f}%",
+             "    " + " ".join(f"{c:>4}" for c in _COLUMNS[:S])]
+    for y in range(S):
+        lines.append(f"{S - y:>3} " + " ".join(f"{int(round(100 * v)):>+4d}" for v in t[y]))
+    return "\n".join(lines)
+
+
+def format_analysis(record, board_size, top=5, ownership=None):
     """A table of the `top` candidate moves of one `analyse` record: one line per candidate in descending visits (ties: ascending
     action) with its vertex, visits, q, prior and its line -- the principal variation for the move that heads it, the move alone
-    for the others.  A q that is NaN (never visited) prints as '-'."""
+    for the others.  A q that is NaN (never visited) prints as '-'.  `ownership`: a `playout_ownership` record of the same
+    position, printed underneath (format_ownership)."""
     visits, prior, q = np.asarray(record["visits"]), np.asarray(record["prior"]), np.asarray(record["q"])
     legal = np.asarray(record["legal"]) if "legal" in record else (visits > 0) | (prior > 0)
     cand = sorted(np.flatnonzero(legal), key=lambda a: (-int(visits[a]), int(a)))[:max(int(top), 0)]
@@ -76,4 +115,6 @@ def format_analysis(record, board_size, top=5):
         line = pv if pv and pv[0] == a else [a]
         lines.append(f"{vertex(a, board_size):<5}{int(visits[a]):>8}{qs:>8}{float(prior[a]):>8.4f}  "
                      + " ".join(vertex(m, board_size) for m in line))
+    if ownership is not None:
+        lines.append(format_ownership(ownership, board_size))
     return "\n".join(lines)

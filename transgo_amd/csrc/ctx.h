@@ -38,7 +38,7 @@ struct tg_ctx {
     std::string err;
     tg::RulesCfg rules;
     // env scratch
-    tg::DevBuf env_in, env_out, env_act, env_flags, env_u8, env_f32, env_i32;
+    tg::DevBuf env_in, env_out, env_act, env_flags, env_u8, env_f32, env_i32, env_rng, env_moves;
     tg::Engine* eng = nullptr;
 };
 

@@ -67,6 +67,49 @@ class GoEnv:
                       g("player"), g("step"), g("terminated"))
         return r
 
+    ROLLOUT_POLICIES = {"noeye": 0, "legal": 1}               # TG_ROLLOUT_NOEYE / TG_ROLLOUT_LEGAL
+
+    def seed_streams(self, seeds):
+        """np.random.seed(seed) per board -> [n, sizeof(tg_mt19937)] uint8 (624 key words + position), the form `streams` takes."""
+        seeds = np.asarray(seeds).reshape(-1)
+        st = (_lib.TgMt19937 * len(seeds))()
+        for k, s in enumerate(seeds):
+            self.ctx.lib.tg_host_mt_seed(st[k], int(s) % (2 ** 32))
+        return np.frombuffer(st, np.uint8).reshape(len(seeds), -1).copy()
+
+    def rollout_batch(self, states, seeds=None, streams=None, max_plies=None, policy="noeye", record=False):
+        """Uniformly random playouts of n boards in ONE kernel launch (tg_env_rollout): per board, until the game ends or
+        max_plies (an int or one per board; None = to the end) plies are played, the side to move plays rs.choice(candidates) --
+        "noeye": getLegalNoEye without pass (own true eyes are never filled), "legal": the pass-filtered getLegalAction, the list
+        the reference's RandomBot draws from (test_trans.py:14-23) -- and passes only when no candidate is left.  rs is NumPy's
+        legacy RandomState: `seeds` = np.random.seed(seed) per board, `streams` = the streams an earlier call returned, to go on
+        from.  -> dict(states, plies int32[n], done bool[n], streams[, moves int32[n][cap], -1 behind the last ply])."""
+        states = np.ascontiguousarray(states, np.uint8)
+        n = states.shape[0]
+        if (seeds is None) == (streams is None):
+            raise ValueError("rollout_batch takes either seeds or streams")
+        if policy not in self.ROLLOUT_POLICIES:
+            raise ValueError(f"unknown rollout policy {policy!r}")
+        rng = self.seed_streams(seeds) if streams is None else np.array(streams, np.uint8, order="C")
+        if rng.shape != (n, ctypes.sizeof(_lib.TgMt19937)):
+            raise ValueError("one stream per board")
+        budget = None
+        if max_plies is not None:
+            budget = np.ascontiguousarray(np.broadcast_to(np.asarray(max_plies, np.int64), (n,)))
+            if (budget < 0).any():
+                raise ValueError("negative ply budget")
+            budget = np.minimum(budget, self.max_step).astype(np.int32)       # a game never has more than max_step plies
+        out = np.empty_like(states)
+        plies = np.zeros(n, np.int32); done = np.zeros(n, np.uint8)
+        cap = max(int(budget.max()) if budget is not None and n else self.max_step, 1)
+        moves = np.full((n, cap), -1, np.int32) if record else None
+        self.ctx.call("tg_env_rollout", _ptr(states), _ptr(out), n, _ptr(rng), None if budget is None else _ptr(budget),
+                      self.ROLLOUT_POLICIES[policy], _ptr(plies), _ptr(done), None if moves is None else _ptr(moves), cap)
+        r = dict(states=out, plies=plies, done=done.astype(bool), streams=rng)
+        if record:
+            r["moves"] = moves
+        return r
+
     # ---- reference surface (one state per call) -------------------------------------------------------------------------
     @staticmethod
     def _one(state):

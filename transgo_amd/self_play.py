@@ -669,6 +669,71 @@ class SelfPlay:
             e.close()
         return win_ratio, info2, info3
 
+    def evaluate_random(self, n_games=20, seed=0, evaluators=None, policy="legal", weights=None, shared_storage_worker=None):
+        """A strength gate against the uniform random player (the reference's evaluate2, test_trans.py:60-95, agent against
+        RandomBot, :14-23): the network moves by select_action exactly as in policy_evaluate, the random player plays
+        rs.choice(candidates) -- policy "legal": the pass-filtered getLegalAction RandomBot draws from (environment.py:121-129);
+        "noeye": getLegalNoEye (environment.py:161-164) without pass -- the network's colour alternates from BLACK game by game,
+        and all n_games run concurrently on ONE engine.  Game i owns the stream np.random.seed(seed + i): the search's tie breaks
+        and its temperature draw AND the random player's draws come from it (NumPy's legacy stream; the reference's RandomBot
+        uses Python's `random`), so a game equals the sequential game after np.random.seed(seed + i) with the bot drawing
+        np.random.choice (tests/test_gpu_playout.py checks that against the oracle).  The random player's move is a
+        GoEnv.rollout_batch of one ply (tg_env_rollout) over the games where it is to move.  The network: `evaluators` (a host
+        callable, or {"train": fn}; parity tests), else `weights` (a state_dict), else the storage's "weights".  Nothing is
+        written to a storage and nothing is promoted.  Returns (win_ratio, winners[n_games], colours[n_games])."""
+        from .environment import GoEnv
+        cfg, w = self.config, self.worker
+        n_games = int(n_games)
+        if n_games <= 0:
+            raise ValueError("n_games must be positive")
+        fn = evaluators.get("train") if isinstance(evaluators, dict) else evaluators
+        if fn is None:
+            if weights is None and shared_storage_worker is not None:
+                weights = _get(_call(shared_storage_worker.get_info, "weights"))
+            if weights is None:
+                raise ValueError("evaluate_random needs evaluators, weights or a storage that holds \"weights\"")
+        eng = SelfPlayEngine(
+            n_games, board_size=cfg.board_size, num_simulation=cfg.num_simulation, parallel_readouts=cfg.parallel_readouts,
+            c_puct1=cfg.c_puct1, c_puct2=cfg.c_puct2, wu_loss=cfg.wu_loss, komi=cfg.komi, max_step=cfg.max_step,
+            encode_dim=cfg.encode_state_channels, net_blocks=w.blocks, net_filters=w.filters, device=w.device,
+            net_precision=getattr(cfg, "inference_dtype", "f32"), evaluator=fn, record_games=False)
+        try:
+            if fn is None:
+                arch = w.arch
+                if "main_network.res_conv2.conv_1.weight" in weights and not arch.policy_attention:
+                    arch = _model.transgo_arch()
+                _model.load_into(eng.ctx, weights, cfg.board_size, cfg.encode_state_channels, w.filters, arch=arch)
+            eng.reset(np.zeros(n_games, np.uint32))                 # brings the engine up; the streams that count are set per ply
+            env = GoEnv(cfg, device=w.device)
+            states = env.reset_batch(n_games)
+            streams = env.seed_streams(int(seed) + np.arange(n_games, dtype=np.int64))      # np.random.seed(seed + i) for game i
+            colours = np.where(np.arange(n_games) % 2 == 0, 1, 2)    # the network's colour in game i
+            done = np.zeros(n_games, bool)
+            ply = 0
+            while not done.all():
+                to_move = 1 if ply % 2 == 0 else 2                   # every live game is at the same ply
+                net = ~done & (colours == to_move)
+                bot = ~done & (colours != to_move)
+                if net.any():
+                    eng.set_rng_streams(streams)
+                    acts = eng.select_action(states, net.astype(np.uint8))
+                    streams[net] = eng.rng_streams()[net]
+                    nxt, d, _ = env.step_batch(states, np.where(net, acts, cfg.board_size ** 2))
+                    states[net] = nxt[net]
+                    done |= d & net
+                if bot.any():
+                    idx = np.flatnonzero(bot)
+                    r = env.rollout_batch(states[idx], streams=streams[idx], max_plies=1, policy=policy)
+                    states[idx], streams[idx] = r["states"], r["streams"]
+                    done[idx] |= r["done"]
+                ply += 1
+            score = env.query_batch(states, score=True)["score"]
+            winners = np.where(score > 0, 1, 2).astype(np.int64)      # environment.py:118-119
+            self.last_random_evaluation = {"winners": winners, "colours": colours, "streams": streams}
+            return float((winners == colours).sum()) / n_games, winners, colours
+        finally:
+            eng.close()
+
     def continuous_self_play(self, shared_storage_worker, mem, max_moves=None):
         """self_play.py:902-983 for G games per rank at once.  Finished games are gathered to rank 0
         (transgo_amd.distributed.gather_harvest: the RCCL exchange that replaces the per-tuple Ray RPCs of :956,:965) and only
