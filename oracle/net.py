@@ -165,7 +165,7 @@ def _residual_blocks(net):
     return [m for m in net.main_network.modules() if isinstance(m, PreActBlock)]
 
 
-def parity_weights(net, seed, calib=None, res_gain=None, att_logit=2.0, act_gain=1.0, vo_gain=1.0):
+def parity_weights(net, seed, calib=None, res_gain=None, att_logit=2.0, act_gain=1.0, vo_gain=1.0, head_scales=None):
     """Re-initialise `net` (a TowerNetwork or TransGoMain) in place with weights under which every layer visibly moves the outputs,
     for the float64 parity tests: seeded torch's default init leaves the network nearly constant (policy 0.010-0.014, values within
     0.02), so a kernel that dropped a whole input channel still passes a 1e-3 check.  Here conv and linear weights are He-scaled
@@ -175,8 +175,11 @@ def parity_weights(net, seed, calib=None, res_gain=None, att_logit=2.0, act_gain
     largest weight of a row ~e^5 times the mean; sharper ones make the f32 forward itself ill-conditioned); the dense heads are scaled
     by act_gain (policy) and vo_gain (value, ownership) -- or, given calibration positions `calib`, rescaled on them so that
     the smallest per-row policy logit spread is 2 (at most 14 for the widest row) and the largest |pre-tanh| of value and
-    ownership is 2: how far the trunk's scale drifts depends on depth, width and seed.  The properties the tests rely on are
-    asserted by the tests, not assumed here.  Returns `net`."""
+    ownership is 2: how far the trunk's scale drifts depends on depth, width and seed.  The two factors of that rescaling come out
+    of an f32 forward, whose last bits differ between machines and thread counts; they are left in net.head_scales, and
+    `head_scales` applies a pair measured elsewhere instead -- everything else is elementwise arithmetic on the seeded generator's
+    numbers, so the weights are then the same bits everywhere.  The properties the tests rely on are asserted by the tests, not
+    assumed here.  Returns `net`."""
     g = torch.Generator().manual_seed(seed)
     body = net.main_network
     blocks = _residual_blocks(net)
@@ -210,27 +213,31 @@ def parity_weights(net, seed, calib=None, res_gain=None, att_logit=2.0, act_gain
                 m.query_conv.weight.mul_(s); m.key_conv.weight.mul_(s)
         body.fc_val.weight.mul_(vo_gain); body.fc_own.weight.mul_(vo_gain)
         body.fc_act.weight.mul_(act_gain)
-        if calib is not None:
+        if calib is not None and head_scales is None:
             out = {}
             hs = [getattr(body, k).register_forward_hook(lambda m, i, o, k=k: out.__setitem__(k, o - m.bias)) for k in ("fc_act", "fc_val", "fc_own")]
             net.main_prediction(torch.as_tensor(calib, dtype=torch.float32))
             for h in hs:
                 h.remove()
             spread = out["fc_act"].max(1).values - out["fc_act"].min(1).values
-            body.fc_act.weight.mul_(min(2.0 / float(spread.min()), 14.0 / float(spread.max())))
-            vo = 2.0 / max(float(out["fc_val"].abs().max()), float(out["fc_own"].abs().max()))
+            head_scales = (min(2.0 / float(spread.min()), 14.0 / float(spread.max())),
+                           2.0 / max(float(out["fc_val"].abs().max()), float(out["fc_own"].abs().max())))
+        if head_scales is not None:
+            act, vo = head_scales
+            body.fc_act.weight.mul_(act)
             body.fc_val.weight.mul_(vo); body.fc_own.weight.mul_(vo)
+            net.head_scales = (act, vo)
     return net
 
 
-def parity_tower(board_size=9, input_dim=10, filters=128, blocks=6, seed=1234, calib=None):
-    """TowerNetwork with parity_weights (see there), head scales calibrated on the positions `calib`."""
-    return parity_weights(TowerNetwork(board_size, input_dim, filters, blocks).eval(), seed, calib)
+def parity_tower(board_size=9, input_dim=10, filters=128, blocks=6, seed=1234, calib=None, head_scales=None):
+    """TowerNetwork with parity_weights (see there), head scales calibrated on the positions `calib` or given as `head_scales`."""
+    return parity_weights(TowerNetwork(board_size, input_dim, filters, blocks).eval(), seed, calib, head_scales=head_scales)
 
 
-def parity_transgo(board_size=9, input_dim=10, filters=128, seed=1234, calib=None):
+def parity_transgo(board_size=9, input_dim=10, filters=128, seed=1234, calib=None, head_scales=None):
     """The shipped MainNetwork layout (TransGoMain, attention included) with parity_weights."""
-    return parity_weights(TransGoMain(board_size, input_dim, filters).eval(), seed, calib)
+    return parity_weights(TransGoMain(board_size, input_dim, filters).eval(), seed, calib, head_scales=head_scales)
 
 
 def float64_forward(net, x, block_hook=None):

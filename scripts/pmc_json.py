@@ -41,14 +41,14 @@ for k in sorted(set(fe) | set(wr)):
     e = {"launches_summarised": len(f), "grid_size_median": grid, "FETCH_SIZE_KB_raw_median": round(fk, 1), "WRITE_SIZE_KB_median": round(wk, 1),
          "hbm_bytes_per_launch": round((2 * fk + wk) * 1024.0, 1), "duration_us_median": round(statistics.median(x[2] for x in f) / 1e3, 2)}
     if conv:
-        targs = [t.strip(" >") for t in k.split(",")]                                         # k_conv3x3_sg<S, F, EPI[, SIN, SOUT]>
+        targs = [t.strip(" >") for t in k.split(",")]                                         # k_conv3x3_sg<S, F, EPI, SIN, SOUT>
         epi = int(targs[2])
         rows = grid / 256 * 128                        # one workgroup per (128 boards, position): workgroups * 128 = boards * P = rows
         # EPI 1 reads h and the residual and writes the stream: 12F bytes per row; the two-tensor chain (no SIN / SOUT) also wrote
         # the next block's activated input, 16F.  Told apart by the template arguments, which holds for what this script is run on:
-        # the default arm (or TG_ONE_STREAM=0) of a pure tower -- TG_ONE_STREAM=2 writes the copy from <.., true, true> too, and a
-        # block between attention layers or in front of the head writes none from <.., false, false>
-        alg = (8 * F if epi == 0 else 12 * F if "true" in targs[3:] else 16 * F) * rows
+        # the default arm (or TG_ONE_STREAM=0) of a pure tower -- a block between attention layers or in front of the head writes
+        # none from <.., false, false>
+        alg = (8 * F if epi == 0 else 12 * F if "true" in targs[3:5] else 16 * F) * rows
         e.update(boards_per_workgroup=128, rows_per_launch_approx=int(rows), algorithmic_bytes_per_launch=int(alg),
                  traffic_over_algorithmic=round(e["hbm_bytes_per_launch"] / alg, 3))
     out["kernels"][k] = e

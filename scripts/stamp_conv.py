@@ -3,8 +3,7 @@ net.hip with -DTG_CONV_STAMP, `scripts/build_variant.sh cstamp net.hip -DTG_CONV
 the GPU box; the shipped library has no stamp).  `python scripts/stamp_conv.py [rows blocks]`: forwards of a 9x9 / F = 128 tower as
 scripts/time_net.py runs them; the stamps are those of lane 0 of wave 0 of six workgroups of XCD 0 in the last conv1 launch and the
 last stream-to-stream conv2 launch: the first interior, edge and corner position of board range 0 (first round) and of range 7 (the
-middle of the XCD's run).  TG_CONV_FIXED_PART=0 in the environment stamps the earlier prologue.  Read the SHARES: the stamps fence
-the scheduler, the build is slower than the product."""
+middle of the XCD's run).  Read the SHARES: the stamps fence the scheduler, the build is slower than the product."""
 import ctypes, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -29,9 +28,9 @@ assert fn(out, 96) == 0
 s = np.array([int(v) for v in out], dtype=np.int64).reshape(2, 2, 3, 8)           # [EPI][round][class][phase]
 # The unit is the tick of __builtin_readcyclecounter.  It is NOT the 10 ns of s_memrealtime: an interior workgroup's walk of 72 stages
 # reads ~480 k ticks while a launch of 9936 workgroups on 1024 slots takes ~2.4 ms (~250 us per workgroup), about 0.5 ns per tick.
-print(f"TG_CONV_FIXED_PART={os.environ.get('TG_CONV_FIXED_PART', '(unset: shortened fixed part)')}; rows {B}, blocks {NB}; stamped build: "
+print(f"rows {B}, blocks {NB}; stamped build: "
       f"{n.value} conv launches, {ms.value / n.value:.3f} ms on average (not the product's time)")
-names = ["entry -> bias|s2|t2 issued (FP) / in LDS (earlier prologue)", "-> weight DMAs of the prologue issued", "-> first counted wait + barrier passed",
+names = ["entry -> bias (|s2|t2) issued", "-> weight DMAs of the prologue issued", "-> first counted wait + barrier passed",
          "-> first MFMAs issued (B fragments, residual landed)", "-> end of the walk", "-> epilogue: every store issued", "-> stores written"]
 for e, kern in enumerate(("conv1 <9,128,0,SIN>", "conv2 <9,128,1,SIN,SOUT>")):
     for r, rnd in enumerate(("first round (range 0)", "middle round (range 7)")):

@@ -223,9 +223,11 @@ def test_fp16_residual_stream_mode(S, F, NB, n):
 
 
 def test_f32_conv_both_tile_shapes():
-    """k_conv3x3_sg at F = 128 is built with 192-row and 128-row tiles and the host picks per launch by the batch's round count:
-    1700 positions (137 700 rows: one round of 768 x 192, two of 1024 x 128) take the large tiles, 1500 (121 500 rows) the small
-    ones; both against fp32 torch, and the rows they share must agree bit for bit (the tile shape does not change the k order)."""
+    """k_conv3x3_sg at F = 128 has one tile shape, a workgroup per (board position, range of 128 boards); the two batch sizes here
+    once chose between two shapes and now differ in how the last range is filled: 1700 positions are 13 full ranges and 36 boards
+    (two of the last workgroups' four waves without a board), 1500 are 11 full ranges and 92 boards.  Both against fp32 torch,
+    and the rows they share must agree bit for bit (a board's result depends on neither the batch size nor where the batch
+    ends)."""
     import torch
     from oracle.net import seeded_tower
     from transgo_amd.model import HipNetwork
@@ -236,8 +238,8 @@ def test_f32_conv_both_tile_shapes():
         p, v, o = [t.numpy() for t in net.main_prediction(torch.from_numpy(x))]
     h = HipNetwork(9, 10, 128, 2, rows_cap=1700)
     h.set_weights(net.get_weights())
-    big = h.main_prediction(x)                       # M = 137700 -> 192-row tiles
-    small = h.main_prediction(x[:1500])              # M = 121500 -> 128-row tiles
+    big = h.main_prediction(x)                       # 13 ranges of 128 boards + 36
+    small = h.main_prediction(x[:1500])              # 11 ranges + 92
     for got, n in ((big, 1700), (small, 1500)):
         assert np.abs(got[0] - p[:n]).max() < TOL and np.abs(got[1] - v[:n]).max() < TOL and np.abs(got[2] - o[:n]).max() < TOL
     assert np.array_equal(big[0][:1500], small[0]) and np.array_equal(big[1][:1500], small[1])

@@ -18,8 +18,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <type_traits>
-#include <utility>
 #include <vector>
 
 #include "conv_rows.h"
@@ -45,7 +43,7 @@ struct Layer { int kind; int ridx; AttW a; };                                   
 //               starts its accumulators from the stream.  Towards an attention layer or the head the stream is row-major, and an
 //               attention layer also writes relu(bn1_next(.)) slice-major (bufAct) for a residual block that follows it.
 //               TG_ONE_STREAM=0 (read at the load, like TG_DMA_CONV) selects the chain this replaced -- a row-major stream and
-//               bufAct behind every producer -- and 2 the single stream with bufAct still written and read (no activation on load)
+//               bufAct behind every producer (the reference of tests/test_gpu_conv_one_stream.py)
 //   CHAIN_F16   fp16 storage, f32 accumulate (k_conv3x3_h2; stem and head conv too); the residual stream stays f32 unless r16
 //   CHAIN_SPLIT split precision ("f32x3"): every conv operand as fp16 hi + lo, three of the four products on the fp16 MFMA; the
 //               residual stream, the dense heads and (beyond the fused k_attention_x3) attention stay f32
@@ -57,9 +55,8 @@ struct NetPath {
     bool att_h = false;        // CHAIN_F16, f32 residual stream: attention blocks on the fused k_attention_h (9x9, F = 128)
     bool head_x2 = false;      // CHAIN_SPLIT: the head conv on k_head_gemm_x2 (F = 128, the trunk ends in a residual block)
     size_t att_lds = 0;        // k_attention's dynamic LDS in bytes; 0: no attention, or its image does not fit
-    int one_stream = 0;        // CHAIN_DMA: 1 between conv layers ONE f32 residual stream in the conv's row order, activated on load
-                               // (default); 2 that stream, relu(bn1_next(.)) still written beside it; 0 (TG_ONE_STREAM=0) two tensors
-    bool conv_fp = true;       // CHAIN_DMA: k_conv3x3_sg with the shortened fixed part (FP); false (TG_CONV_FIXED_PART=0) the earlier prologue
+    bool one_stream = false;   // CHAIN_DMA: between conv layers ONE f32 residual stream in the conv's row order, activated on load
+                               // (default); false (TG_ONE_STREAM=0) two tensors
 };
 
 struct Net {
@@ -421,7 +418,7 @@ __device__ __forceinline__ int swz64(int row) { return ((row >> 2) & 1) << 1; }
 // Stage k = (16-channel slice k / nt, the (k % nt)-th on-board tap), nt = 4 / 6 / 9, so F/16 * nt stages -- always an even count.
 // A (weights): the stage's tile arrives by LDS-DMA from a stage-ordered copy of the weights ([slice*9+tap][cout][16]) into a
 // 4-slot ring (slot = k % 4), two stages per barrier, the next pair landing while this one is used (the prologue: stages 0 and 1
-// in front of the first barrier, 2 and 3 behind it -- see FP below); the LDS image is XOR-swizzled
+// in front of the first barrier, 2 and 3 behind it -- see "the fixed part" below); the LDS image is XOR-swizzled
 // at the source (swz64) so ds_read_b128 fragments are conflict-free.  Stages per barrier at F = 128, measured on the row-ordered
 // kernel: 2: 138.5, 3: 131.6, 4: 127.1 TFLOP/s.  B (activations): every wave loads its own B fragments straight from L2 into
 // registers, a stage ahead; a tap is the wave-uniform shift of (dy*S + dx)*16 rows inside the board group.  Everything is at least
@@ -435,10 +432,9 @@ __device__ __forceinline__ int swz64(int row) { return ((row >> 2) & 1) << 1; }
 // in the activating kernel only) and 67 KB, two per CU.  Three tiles per wave
 // (192 boards, three workgroups per CU at F = 128), the better shape of the row-ordered kernel on full rounds, measured 4-7 %
 // slower here at 9x9 and 19x19: the walks differ in length, and four shorter waves per SIMD fill each other's gaps better.
-// The fixed part of a workgroup (FP, the default; FP = false is the prologue this replaced, kept as TG_CONV_FIXED_PART=0 for the A/B
-// and the bit-identity test -- every accumulation runs in the same order in both):
+// The fixed part of a workgroup, what it pays before its first MFMA:
 //  * bias | s2 | t2 are fetched into registers FIRST and written to `par` behind everything the prologue issues, so their round
-//    trip runs beside the weight DMAs instead of in front of them (the first barrier publishes `par` as before);
+//    trip runs beside the weight DMAs instead of in front of them (the first barrier publishes `par`);
 //  * the first barrier waits for the weight stages 0 and 1 only.  vmcnt retires in order, so what the first MFMA needs is issued
 //    first: stages 0 and 1, the B fragments of stage 0, then (EPI 1) the residual in the order of use, ct-major.  Stages 2 and 3
 //    go out behind the barrier and behind the first consumer of those loads (act_b, or an empty asm: the compiler waits for them
@@ -456,7 +452,7 @@ __device__ unsigned long long g_conv_stamp[2 * 6 * 8];                  // [EPI]
 #else
 #define TG_CSTAMP(i) do { } while (0)
 #endif
-template <int S, int F, int EPI, bool SIN = false, bool SOUT = false, bool FP = true>
+template <int S, int F, int EPI, bool SIN = false, bool SOUT = false>
 __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const float* __restrict__ in, float* __restrict__ out,
                                                                        const float* __restrict__ res, const float* __restrict__ Ws,
                                                                        const float* __restrict__ bias, float* __restrict__ out2,
@@ -496,14 +492,10 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
     if (cslot >= 0 && lane == 0) g_conv_stamp[cslot * 8] = t_entry;
 #endif
     static_assert(F <= 256, "one parameter triple per thread");
-    [[maybe_unused]] float pbias = 0.f, ps2 = 0.f, pt2 = 0.f;            // FP: this thread's element of bias | s2 | t2, in flight
-    [[maybe_unused]] const bool bn = out2 || ACT;                        // s2 / t2 are in use
-    if constexpr (FP) {                                                  // no branch around the loads (see TG_PAR_LANDED)
-        pbias = bias[tid & (F - 1)]; ps2 = (bn ? s2 : bias)[tid & (F - 1)]; pt2 = (bn ? t2 : bias)[tid & (F - 1)];
-        __builtin_amdgcn_sched_barrier(0);                               // issued here, ahead of the weight DMAs
-    } else {
-        for (int i = tid; i < F; i += 256) { par[i] = bias[i]; par[F + i] = out2 || ACT ? s2[i] : 0.f; par[2 * F + i] = out2 || ACT ? t2[i] : 0.f; }
-    }
+    const bool bn = out2 || ACT;                                         // s2 / t2 are in use
+    // this thread's element of bias | s2 | t2, in flight; no branch around the loads (see TG_PAR_LANDED)
+    float pbias = bias[tid & (F - 1)], ps2 = (bn ? s2 : bias)[tid & (F - 1)], pt2 = (bn ? t2 : bias)[tid & (F - 1)];
+    __builtin_amdgcn_sched_barrier(0);                                   // issued here, ahead of the weight DMAs
     TG_CSTAMP(1);
 
     // the workgroup's walk: nt on-board taps, packed 4 bits each; k / nt by a multiplication that is exact far beyond NSL * 9
@@ -558,21 +550,18 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
             for (int e = 0; e < 4; ++e) dst[t][e] = bn_relu_unpacked(b[t][e], bsc[e], bsh[e]);
     };
     constexpr int NRES = EPI == 1 ? CT * NPT : 0;                        // residual loads per lane
-    // FP: the triple is older than the DMAs just waited for.  It is taken over by an asm that differs between the two paths, so that
+    // The triple is older than the DMAs just waited for.  It is taken over by an asm that differs between the two paths, so that
     // the compiler's wait for it stands on each path with that path's count (behind a merged tail it is vmcnt(0), and the barrier
     // would wait for the residual too)
-#define TG_PAR_LANDED(PATH) do { if constexpr (FP) asm volatile("; bias, s2, t2 landed: " PATH : "+v"(pbias), "+v"(ps2), "+v"(pt2)); } while (0)
-#pragma unroll
-    for (int k = 0; k < (FP ? 2 : D); ++k) dma_w(k);
+#define TG_PAR_LANDED(PATH) asm volatile("; bias, s2, t2 landed: " PATH : "+v"(pbias), "+v"(ps2), "+v"(pt2))
+    dma_w(0); dma_w(1);
     TG_CSTAMP(2);
     if (active) {
-        if constexpr (FP) {
-            load_b(b_cur, 0);
-            __builtin_amdgcn_sched_barrier(0);                           // ahead of the residual: the first MFMA needs them first
-        }
+        load_b(b_cur, 0);
+        __builtin_amdgcn_sched_barrier(0);                               // ahead of the residual: the first MFMA needs them first
 #pragma unroll
         for (int i = 0; i < CT * NPT; ++i) {                             // EPI 1: start from the residual (no loads behind the epilogue's stores)
-            const int ct = FP ? i / NPT : i % CT, t = FP ? i % NPT : i / CT;   // FP: in the order of use
+            const int ct = i / NPT, t = i % NPT;                         // in the order of use
             const int b = (grp0 + t) * 16 + j;
             [[maybe_unused]] const int m = b < rows ? b * P + p : M - 1;
             {
@@ -588,7 +577,6 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
                 }
             }
         }
-        if constexpr (!FP) load_b(b_cur, 0);
         // The barrier must see the weight DMAs of the first stages landed; the operations issued after them -- CT*NPT residual
         // loads, NPT B fragments -- are the wave's youngest and are waited for by the compiler, one by one, in front of the MFMA
         // that first needs each.
@@ -599,9 +587,7 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
         TG_PAR_LANDED("wave without boards");
     }
 #undef TG_PAR_LANDED
-    if constexpr (FP) {
-        if (tid < F) { par[tid] = pbias; par[F + tid] = bn ? ps2 : 0.f; par[2 * F + tid] = bn ? pt2 : 0.f; }
-    }
+    if (tid < F) { par[tid] = pbias; par[F + tid] = bn ? ps2 : 0.f; par[2 * F + tid] = bn ? pt2 : 0.f; }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     TG_BARRIER();
     TG_CSTAMP(3);
@@ -612,21 +598,19 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
             for (int t = 0; t < NPT; ++t) b_cur[t] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     }
-    if constexpr (FP) {
-        // Stages 2 and 3 go out behind the first consumer of everything loaded above: the compiler waits for those loads with
-        // vmcnt(0) (the accumulators are live into a loop), which must not include two more weight stages.
-        if (active) {
+    // Stages 2 and 3 go out behind the first consumer of everything loaded above: the compiler waits for those loads with
+    // vmcnt(0) (the accumulators are live into a loop), which must not include two more weight stages.
+    if (active) {
 #pragma unroll
-            for (int t = 0; t < NPT; ++t) {
-                if constexpr (!ACT) asm volatile("" : "+v"(b_cur[t]));
-                if constexpr (EPI == 1) {
+        for (int t = 0; t < NPT; ++t) {
+            if constexpr (!ACT) asm volatile("" : "+v"(b_cur[t]));
+            if constexpr (EPI == 1) {
 #pragma unroll
-                    for (int ct = 0; ct < CT; ++ct) asm volatile("" : "+v"(acc[ct][t]));
-                }
+                for (int ct = 0; ct < CT; ++ct) asm volatile("" : "+v"(acc[ct][t]));
             }
         }
-        dma_w(2); dma_w(3);
     }
+    dma_w(2); dma_w(3);
 
 #pragma unroll 1
     for (int k0 = 0; k0 < nst; k0 += 2) {
@@ -656,10 +640,10 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
                     __builtin_amdgcn_sched_barrier(0);                   // behind the stage's MFMAs: the fragments are a stage old here
                     act_b(b_cur, b_next);
                 } else {
-                    if constexpr (FP) __builtin_amdgcn_sched_barrier(0); // the same place for the fragments' wait
+                    __builtin_amdgcn_sched_barrier(0);                   // the same place for the fragments' wait
 #pragma unroll
                     for (int t = 0; t < NPT; ++t) {
-                        if constexpr (FP) asm volatile("" : "+v"(b_next[t]));
+                        asm volatile("" : "+v"(b_next[t]));
                         b_cur[t] = b_next[t];
                     }
                 }
@@ -2139,11 +2123,11 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
     // The DMA chain's residual stream between two conv layers (stem or residual block -> residual block) is ONE tensor, slice-major
     // in the conv's row order (conv_rows.h): the producer writes only it (`sout`), the consumer's conv1 activates it on load and its
     // conv2 starts its accumulators from it (`sin`).  Towards an attention layer or the head the stream is row-major as before, and an
-    // attention layer hands a residual block relu(bn1(.)) in bufAct.  one_stream 2 keeps writing bufAct beside the slice-major stream
-    // (conv1 reads it, nothing is activated on load); 0 is the two-tensor chain.
-    const int one = chain == CHAIN_DMA ? n->path.one_stream : 0;
+    // attention layer hands a residual block relu(bn1(.)) in bufAct.  Without one_stream (TG_ONE_STREAM=0) it is the two-tensor chain:
+    // row-major stream, bufAct behind every producer.
+    const bool one = chain == CHAIN_DMA && n->path.one_stream;
     auto conv_layer = [&](size_t j) { return j < nl && n->layers[j].kind == 0; };
-    float* const act2 = one == 1 ? nullptr : n->bufAct;              // relu(bn1_next(.)) beside a conv layer's output
+    float* const act2 = one ? nullptr : n->bufAct;                   // relu(bn1_next(.)) beside a conv layer's output
     auto stem = [&](bool act, const float* sn, const float* tn, bool sout) {   // conv 16 -> F into the residual stream x
         if constexpr (WIDE) {
             if (h16) {   // input planes are 0/1, exact in fp16; 16 planes padded to 64 channels = 18 stages
@@ -2177,20 +2161,14 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
             if (chain == CHAIN_DMA) {
                 // one workgroup per (range of 128 boards, position), the count rounded up to the XCD-contiguous order's multiple of 8
                 const int grid_sd = ((rows + 127) / 128 * P + 7) / 8 * 8;
-                const bool onload = sin && one == 1;                 // conv1 reads the stream itself, else its activated copy
-                auto pick = [&](auto fp) {                           // the two prologues of every variant (TG_CONV_FIXED_PART)
-                    constexpr bool FP = decltype(fp)::value;
-                    auto* c1 = onload ? &k_conv3x3_sg<S, F, 0, true, false, FP> : &k_conv3x3_sg<S, F, 0, false, false, FP>;
-                    auto* c2 = sin ? (sout ? &k_conv3x3_sg<S, F, 1, true, true, FP> : &k_conv3x3_sg<S, F, 1, true, false, FP>)
-                                   : (sout ? &k_conv3x3_sg<S, F, 1, false, true, FP> : &k_conv3x3_sg<S, F, 1, false, false, FP>);
-                    return std::make_pair(c1, c2);
-                };
-                const auto ks = n->path.conv_fp ? pick(std::true_type{}) : pick(std::false_type{});
-                auto* k1 = ks.first;
-                auto* k2 = ks.second;
+                // conv1 activates the stream on load (sin), or reads the copy that an attention layer (or, in the two-tensor chain, any
+                // producer) left activated in bufAct
+                auto* k1 = sin ? &k_conv3x3_sg<S, F, 0, true> : &k_conv3x3_sg<S, F, 0>;
+                auto* k2 = sin ? (sout ? &k_conv3x3_sg<S, F, 1, true, true> : &k_conv3x3_sg<S, F, 1, true>)
+                               : (sout ? &k_conv3x3_sg<S, F, 1, false, true> : &k_conv3x3_sg<S, F, 1>);
                 { ProfScope ps(n, st, conv_flops);
-                  hipLaunchKernelGGL(k1, dim3(grid_sd), dim3(256), 0, st, onload ? x : n->bufAct, n->bufH, nullptr, b.g1, b.c1.b, nullptr,
-                                     onload ? b.s1 : nullptr, onload ? b.t1 : nullptr, rows); }
+                  hipLaunchKernelGGL(k1, dim3(grid_sd), dim3(256), 0, st, sin ? x : n->bufAct, n->bufH, nullptr, b.g1, b.c1.b, nullptr,
+                                     sin ? b.s1 : nullptr, sin ? b.t1 : nullptr, rows); }
                 { ProfScope ps(n, st, conv_flops);
                   hipLaunchKernelGGL(k2, dim3(grid_sd), dim3(256), 0, st, n->bufH, out, x, b.g2, b.c2.b, act ? act2 : nullptr, sn, tn, rows); }
                 return;
@@ -2511,10 +2489,8 @@ NetPath net_path(int S, int F, int prec, const std::string& trunk, bool pol) {
     else if (F == 128 || F == 256) {                                    // attention layers: k_attention_mfma (9x9), k_attention_t (19x19)
         const char* dma = getenv("TG_DMA_CONV");
         p.chain = dma && atoi(dma) == 0 ? CHAIN_F32 : CHAIN_DMA;
-        const char* one = getenv("TG_ONE_STREAM");                      // 0: two tensors (the A/B arm); 2: one stream, bufAct kept
-        p.one_stream = one && one[0] >= '0' && one[0] <= '2' && !one[1] ? one[0] - '0' : 1;   // anything but one digit 0..2: the default
-        const char* fp = getenv("TG_CONV_FIXED_PART");                  // 0: k_conv3x3_sg's earlier prologue (the A/B arm)
-        p.conv_fp = !(fp && fp[0] == '0' && !fp[1]);
+        const char* one = getenv("TG_ONE_STREAM");                      // 0: two tensors (the A/B arm)
+        p.one_stream = !(one && one[0] == '0' && !one[1]);
     }
     p.r16 = prec == 2;
     p.att_x3 = prec == 3 && any_att && F == 128 && S == 9;
@@ -2592,7 +2568,7 @@ int tg_net_load_arch(tg_ctx* ctx, const char* arch_c, const float* blob, size_t 
         if (pol) TG_HIP(ctx, hipMalloc((void**)&n->hca, sizeof(float) * (size_t)rows_cap * P * 16));
         const size_t wcopy = (size_t)(NB > 0 ? 2 * NB : 1) * 9 * F * F;
         // relu(bn1(.)) beside the stream: only an attention layer hands it to a residual block once the conv layers share one stream
-        if (p.chain == CHAIN_DMA && (p.one_stream != 1 || trunk.find("AR") != std::string::npos)) TG_HIP(ctx, hipMalloc((void**)&n->bufAct, act_sm));
+        if (p.chain == CHAIN_DMA && (!p.one_stream || trunk.find("AR") != std::string::npos)) TG_HIP(ctx, hipMalloc((void**)&n->bufAct, act_sm));
         for (Net::WeightSet& w : n->sets) {
             TG_HIP(ctx, hipMalloc((void**)&w.blob, sizeof(float) * n_floats));
             TG_HIP(ctx, hipMalloc((void**)&w.head_g, sizeof(float) * 64 * (size_t)F));
@@ -2796,15 +2772,6 @@ int tg_net_stream_layout(tg_ctx* ctx, int* one_stream, int* act_copy) {
     const Net* n = ctx->eng->net;
     if (one_stream) *one_stream = n->path.chain == CHAIN_DMA ? n->path.one_stream : 0;
     if (act_copy) *act_copy = n->bufAct != nullptr;
-    return TG_OK;
-}
-
-// 1 where the loaded network's F->F convs run k_conv3x3_sg with the shortened fixed part, 0 with the earlier prologue
-// (TG_CONV_FIXED_PART=0) and on every other chain
-int tg_net_conv_fixed_part(tg_ctx* ctx, int* fixed_part) {
-    if (!ctx || !ctx->eng || !ctx->eng->net || !fixed_part) return TG_ERR_STATE;
-    const Net* n = ctx->eng->net;
-    *fixed_part = n->path.chain == CHAIN_DMA && n->path.conv_fp;
     return TG_OK;
 }
 
