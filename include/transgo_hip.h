@@ -322,9 +322,9 @@ int tg_net_load_poll(tg_ctx* ctx, int wait, int* pending);
 /* main_prediction (model.py:17-20) on host buffers: obs f32[n][C][S][S] -> policy f32[n][A] (softmax), value f32[n]
  * (tanh), own f32[n][S*S] (tanh; may be NULL). */
 int tg_net_predict(tg_ctx* ctx, const float* obs, int n_rows, float* policy, float* value, float* own);
-/* How the loaded network carries its f32 residual stream: one_stream = 1 where the DMA-fed f32 chain keeps ONE slice-major
- * stream between conv layers and activates it on load, 0 for the two-tensor chain (TG_ONE_STREAM=0) and every other chain;
- * act_copy = 1 while the buffer of the pre-activated copy is allocated.  Either may be NULL. */
+/* How the loaded network carries its f32 residual stream: one_stream = 1 for the DMA-fed f32 chain, which keeps ONE slice-major
+ * stream between conv layers and activates it on load, 0 for every other chain; act_copy = 1 while the buffer of the pre-activated
+ * copy is allocated (the DMA-fed chain with an attention layer in front of a residual block).  Either may be NULL. */
 int tg_net_stream_layout(tg_ctx* ctx, int* one_stream, int* act_copy);
 /* Range report.  The reference network is f32 end to end (model.py:79-114) and accepts any trained checkpoint (model.py:23-27);
  * net_precision 1 / 2 / 3 carry activations as fp16 (3: as fp16 hi + lo) and lose f32's range: beyond +-65504 the fp16 copy is

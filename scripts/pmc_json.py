@@ -44,11 +44,8 @@ for k in sorted(set(fe) | set(wr)):
         targs = [t.strip(" >") for t in k.split(",")]                                         # k_conv3x3_sg<S, F, EPI, SIN, SOUT>
         epi = int(targs[2])
         rows = grid / 256 * 128                        # one workgroup per (128 boards, position): workgroups * 128 = boards * P = rows
-        # EPI 1 reads h and the residual and writes the stream: 12F bytes per row; the two-tensor chain (no SIN / SOUT) also wrote
-        # the next block's activated input, 16F.  Told apart by the template arguments, which holds for what this script is run on:
-        # the default arm (or TG_ONE_STREAM=0) of a pure tower -- a block between attention layers or in front of the head writes
-        # none from <.., false, false>
-        alg = (8 * F if epi == 0 else 12 * F if "true" in targs[3:5] else 16 * F) * rows
+        # EPI 0 reads its input and writes h: 8F bytes per row; EPI 1 reads h and the residual and writes the stream: 12F
+        alg = (8 * F if epi == 0 else 12 * F) * rows
         e.update(boards_per_workgroup=128, rows_per_launch_approx=int(rows), algorithmic_bytes_per_launch=int(alg),
                  traffic_over_algorithmic=round(e["hbm_bytes_per_launch"] / alg, 3))
     out["kernels"][k] = e

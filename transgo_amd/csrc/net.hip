@@ -42,8 +42,8 @@ struct Layer { int kind; int ridx; AttW a; };                                   
 //               writes nothing else, the block's first conv applies relu(bn1(.)) to its B fragments as they land, its second conv
 //               starts its accumulators from the stream.  Towards an attention layer or the head the stream is row-major, and an
 //               attention layer also writes relu(bn1_next(.)) slice-major (bufAct) for a residual block that follows it.
-//               TG_ONE_STREAM=0 (read at the load, like TG_DMA_CONV) selects the chain this replaced -- a row-major stream and
-//               bufAct behind every producer (the reference of tests/test_gpu_conv_one_stream.py)
+//               No launch of this chain uses the second output (`out2`) of k_conv3x3 / k_conv3x3_sg any more: it served the
+//               two-tensor chain this replaced and stays in the kernels only until its removal is measured
 //   CHAIN_F16   fp16 storage, f32 accumulate (k_conv3x3_h2; stem and head conv too); the residual stream stays f32 unless r16
 //   CHAIN_SPLIT split precision ("f32x3"): every conv operand as fp16 hi + lo, three of the four products on the fp16 MFMA; the
 //               residual stream, the dense heads and (beyond the fused k_attention_x3) attention stay f32
@@ -55,8 +55,6 @@ struct NetPath {
     bool att_h = false;        // CHAIN_F16, f32 residual stream: attention blocks on the fused k_attention_h (9x9, F = 128)
     bool head_x2 = false;      // CHAIN_SPLIT: the head conv on k_head_gemm_x2 (F = 128, the trunk ends in a residual block)
     size_t att_lds = 0;        // k_attention's dynamic LDS in bytes; 0: no attention, or its image does not fit
-    bool one_stream = false;   // CHAIN_DMA: between conv layers ONE f32 residual stream in the conv's row order, activated on load
-                               // (default); false (TG_ONE_STREAM=0) two tensors
 };
 
 struct Net {
@@ -66,7 +64,7 @@ struct Net {
     ConvW stem; std::vector<BlockW> blocks; std::vector<Layer> layers; const float* s_end = nullptr; const float* t_end = nullptr;
     bool pol_att = false; AttW patt; ConvW head_a; std::string arch;
     float* bufQ = nullptr; float* hca = nullptr;   // q|k|v projections [rows][P][1.5F]; policy head conv output
-    float* bufAct = nullptr;                       // DMA chain: relu(bn1(.)) for a residual block's first conv where its input is not activated on load
+    float* bufAct = nullptr;                       // DMA chain with an attention layer in front of a residual block ("AR"): relu(bn1(.)) from that layer for the block's first conv
     int prec = 0;                                  // cfg.net_precision: 0 = f32, 1 = fp16 storage + f32 accumulate (k_conv3x3_h2), 2 = 1 + fp16 residual stream,
                                                    // 3 = split precision ("f32x3"): every operand as fp16 hi + lo, three of the four products on the fp16 MFMA, f32 accumulate
     const float* head_g = nullptr; const float* head_ag = nullptr;   // [64][F] head conv weights for k_head_gemm (tap*6 + cout rows)
@@ -2123,11 +2121,11 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
     // The DMA chain's residual stream between two conv layers (stem or residual block -> residual block) is ONE tensor, slice-major
     // in the conv's row order (conv_rows.h): the producer writes only it (`sout`), the consumer's conv1 activates it on load and its
     // conv2 starts its accumulators from it (`sin`).  Towards an attention layer or the head the stream is row-major as before, and an
-    // attention layer hands a residual block relu(bn1(.)) in bufAct.  Without one_stream (TG_ONE_STREAM=0) it is the two-tensor chain:
-    // row-major stream, bufAct behind every producer.
-    const bool one = chain == CHAIN_DMA && n->path.one_stream;
+    // attention layer hands a residual block relu(bn1(.)) in bufAct (`act`, `sn` / `tn`: the attention, fp16 and split kernels take
+    // them; the f32 conv kernels get no second output).  `chain` is this forward's: a batch that fell back to CHAIN_F32 above has no
+    // such stream.
+    const bool one = chain == CHAIN_DMA;
     auto conv_layer = [&](size_t j) { return j < nl && n->layers[j].kind == 0; };
-    float* const act2 = one ? nullptr : n->bufAct;                   // relu(bn1_next(.)) beside a conv layer's output
     auto stem = [&](bool act, const float* sn, const float* tn, bool sout) {   // conv 16 -> F into the residual stream x
         if constexpr (WIDE) {
             if (h16) {   // input planes are 0/1, exact in fp16; 16 planes padded to 64 channels = 18 stages
@@ -2139,7 +2137,7 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
             if (chain == CHAIN_DMA) {
                 auto* k = sout ? &k_conv3x3<S, 16, F, false, 0, 9, 2, true, true> : &k_conv3x3<S, 16, F, false, 0, 9, 2, true>;
                 hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, n->x0, x, nullptr, n->stem.w,
-                                   n->stem.b, nullptr, nullptr, M, act ? act2 : nullptr, sn, tn);
+                                   n->stem.b, nullptr, nullptr, M, nullptr, nullptr, nullptr);
                 return;
             }
         }
@@ -2161,8 +2159,8 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
             if (chain == CHAIN_DMA) {
                 // one workgroup per (range of 128 boards, position), the count rounded up to the XCD-contiguous order's multiple of 8
                 const int grid_sd = ((rows + 127) / 128 * P + 7) / 8 * 8;
-                // conv1 activates the stream on load (sin), or reads the copy that an attention layer (or, in the two-tensor chain, any
-                // producer) left activated in bufAct
+                // conv1 activates the stream on load (sin), or reads the copy that an attention layer left activated in bufAct; conv2
+                // (EPI 1) never reads s2 / t2
                 auto* k1 = sin ? &k_conv3x3_sg<S, F, 0, true> : &k_conv3x3_sg<S, F, 0>;
                 auto* k2 = sin ? (sout ? &k_conv3x3_sg<S, F, 1, true, true> : &k_conv3x3_sg<S, F, 1, true>)
                                : (sout ? &k_conv3x3_sg<S, F, 1, false, true> : &k_conv3x3_sg<S, F, 1>);
@@ -2170,7 +2168,7 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
                   hipLaunchKernelGGL(k1, dim3(grid_sd), dim3(256), 0, st, sin ? x : n->bufAct, n->bufH, nullptr, b.g1, b.c1.b, nullptr,
                                      sin ? b.s1 : nullptr, sin ? b.t1 : nullptr, rows); }
                 { ProfScope ps(n, st, conv_flops);
-                  hipLaunchKernelGGL(k2, dim3(grid_sd), dim3(256), 0, st, n->bufH, out, x, b.g2, b.c2.b, act ? act2 : nullptr, sn, tn, rows); }
+                  hipLaunchKernelGGL(k2, dim3(grid_sd), dim3(256), 0, st, n->bufH, out, x, b.g2, b.c2.b, nullptr, nullptr, nullptr, rows); }
                 return;
             }
         }
@@ -2489,8 +2487,6 @@ NetPath net_path(int S, int F, int prec, const std::string& trunk, bool pol) {
     else if (F == 128 || F == 256) {                                    // attention layers: k_attention_mfma (9x9), k_attention_t (19x19)
         const char* dma = getenv("TG_DMA_CONV");
         p.chain = dma && atoi(dma) == 0 ? CHAIN_F32 : CHAIN_DMA;
-        const char* one = getenv("TG_ONE_STREAM");                      // 0: two tensors (the A/B arm)
-        p.one_stream = !(one && one[0] == '0' && !one[1]);
     }
     p.r16 = prec == 2;
     p.att_x3 = prec == 3 && any_att && F == 128 && S == 9;
@@ -2567,8 +2563,8 @@ int tg_net_load_arch(tg_ctx* ctx, const char* arch_c, const float* blob, size_t 
         if (any_att && !p.att_h) TG_HIP(ctx, hipMalloc((void**)&n->bufQ, sizeof(float) * (size_t)rows_cap * P * Wq));
         if (pol) TG_HIP(ctx, hipMalloc((void**)&n->hca, sizeof(float) * (size_t)rows_cap * P * 16));
         const size_t wcopy = (size_t)(NB > 0 ? 2 * NB : 1) * 9 * F * F;
-        // relu(bn1(.)) beside the stream: only an attention layer hands it to a residual block once the conv layers share one stream
-        if (p.chain == CHAIN_DMA && (!p.one_stream || trunk.find("AR") != std::string::npos)) TG_HIP(ctx, hipMalloc((void**)&n->bufAct, act_sm));
+        // relu(bn1(.)) beside the stream: only an attention layer hands it to a residual block ("AR"), the conv layers share one stream
+        if (p.chain == CHAIN_DMA && trunk.find("AR") != std::string::npos) TG_HIP(ctx, hipMalloc((void**)&n->bufAct, act_sm));
         for (Net::WeightSet& w : n->sets) {
             TG_HIP(ctx, hipMalloc((void**)&w.blob, sizeof(float) * n_floats));
             TG_HIP(ctx, hipMalloc((void**)&w.head_g, sizeof(float) * 64 * (size_t)F));
@@ -2770,7 +2766,7 @@ int tg_net_predict(tg_ctx* ctx, const float* obs, int n_rows, float* policy, flo
 int tg_net_stream_layout(tg_ctx* ctx, int* one_stream, int* act_copy) {
     if (!ctx || !ctx->eng || !ctx->eng->net) return TG_ERR_STATE;
     const Net* n = ctx->eng->net;
-    if (one_stream) *one_stream = n->path.chain == CHAIN_DMA ? n->path.one_stream : 0;
+    if (one_stream) *one_stream = n->path.chain == CHAIN_DMA;
     if (act_copy) *act_copy = n->bufAct != nullptr;
     return TG_OK;
 }
