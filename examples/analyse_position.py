@@ -3,6 +3,7 @@
 search thinks -- per candidate move its visits, value and prior, and the line it expects.
 
     python examples/analyse_position.py            # needs an MI355X; a few seconds
+    python examples/analyse_position.py --symmetry mean8 --playouts 64
 """
 import os
 import sys
@@ -15,7 +16,7 @@ from transgo_amd.engine import SelfPlayEngine                     # noqa: E402
 from transgo_amd.environment import GoEnv                         # noqa: E402
 
 
-def main(moves=("E5", "C3", "G7", "C7"), sims=200, filters=32, blocks=2, board_size=9, playouts=0):
+def main(moves=("E5", "C3", "G7", "C7"), sims=200, filters=32, blocks=2, board_size=9, playouts=0, symmetry="none"):
     env = GoEnv(board_size=board_size)
     state, _ = env.reset()
     names = {analysis.vertex(a, board_size): a for a in range(board_size ** 2 + 1)}
@@ -26,7 +27,8 @@ def main(moves=("E5", "C3", "G7", "C7"), sims=200, filters=32, blocks=2, board_s
     eng = SelfPlayEngine(1, board_size=board_size, num_simulation=sims, net_blocks=blocks, net_filters=filters)
     model.load_into(eng.ctx, model.random_weights(board_size, 10, filters, blocks, seed=3), board_size, 10, filters, blocks)
     eng.reset([0])                                                # seeds the stream the search's tie breaks draw from
-    rec = analysis.analyse(eng, np.frombuffer(state, np.uint8).reshape(1, -1))[0]
+    # --symmetry position | mean8: evaluate every leaf in one orientation chosen from the position, or as the mean over all eight
+    rec = analysis.analyse(eng, np.frombuffer(state, np.uint8).reshape(1, -1), symmetry=symmetry)[0]
     # --playouts N: the network-free Monte-Carlo ownership / score estimate next to the search (N random games in one launch)
     own = analysis.playout_ownership(env, np.frombuffer(state, np.uint8).reshape(1, -1), playouts=playouts)[0] if playouts else None
     print(analysis.format_analysis(rec, board_size, top=8, ownership=own))
@@ -35,4 +37,7 @@ def main(moves=("E5", "C3", "G7", "C7"), sims=200, filters=32, blocks=2, board_s
 
 
 if __name__ == "__main__":
-    main(playouts=int(sys.argv[sys.argv.index("--playouts") + 1]) if "--playouts" in sys.argv else 0)
+    sym = sys.argv[sys.argv.index("--symmetry") + 1] if "--symmetry" in sys.argv else "none"
+    if sym not in ("none", "position", "mean8"):
+        sys.exit("--symmetry takes none, position or mean8")
+    main(playouts=int(sys.argv[sys.argv.index("--playouts") + 1]) if "--playouts" in sys.argv else 0, symmetry=sym)

@@ -322,6 +322,41 @@ int tg_net_load_poll(tg_ctx* ctx, int wait, int* pending);
 /* main_prediction (model.py:17-20) on host buffers: obs f32[n][C][S][S] -> policy f32[n][A] (softmax), value f32[n]
  * (tanh), own f32[n][S*S] (tanh; may be NULL). */
 int tg_net_predict(tg_ctx* ctx, const float* obs, int n_rows, float* policy, float* value, float* own);
+/* Symmetry-aware evaluation.  The network is trained on all eight dihedral images of every position (self_play.py:943-965), so it
+ * may be asked about a position in any of them.  Symmetry s = 0..7 is the augmentation index of that loop, s = 2*(i-1) + f:
+ * T_s(m) = np.rot90(m, i) for i = 1..4, then np.fliplr if f == 1; s = 6 is the identity.  Evaluating a row under s: T_s on each of
+ * its planes, the unchanged forward, and the outputs mapped back to the original orientation (board part of the policy and the
+ * ownership through the inverse permutation, pass entry and value as they are).  Every evaluation of the context -- tg_sp_eval,
+ * tg_sp_search, tg_net_predict -- goes through the mode, in every net_precision:
+ *   TG_SYM_NONE      the plain forward: nothing more is launched or allocated, results are bit-identical to a context that never
+ *                    made this call
+ *   TG_SYM_FIXED     every row under s = arg (tests, diagnostics)
+ *   TG_SYM_POSITION  row r under s = sym_of(arg = seed, the row's bit-packed planes), a pure function of seed and position -- the
+ *                    same position gets the same orientation in whatever batch it appears, so duplicate leaves, a snapshot +
+ *                    restore and a host restatement all agree.  sym_of in uint32 arithmetic over the row's ceil(C*S*S/32) words
+ *                    (bit i = plane-major flat index i, unused high bits of the last word zero): h = seed ^ 0x9E3779B9; per word
+ *                    h = (h ^ w) * 0x01000193; then h ^= h>>16, h *= 0x85EBCA6B, h ^= h>>13, h *= 0xC2B2AE35, h ^= h>>16;
+ *                    s = h >> 29.  No game's MT19937 stream is touched.
+ *   TG_SYM_MEAN8     eight forwards, s = 0..7 in that order; the mapped-back policy, value and ownership accumulate in float32
+ *                    as ((((o0 + o1) + o2) + ...) + o7) * 0.125f.  A background weight refresh is never adopted between the
+ *                    eight passes.
+ * The reference's self-play evaluates in one orientation only (self_play.py:777-786): TG_SYM_NONE alone keeps bit parity with it.
+ * TG_ERR_ARG for an unknown mode or s > 7; TG_ERR_STATE while an evaluation batch is pending (the evaluator changes at a move
+ * boundary only); a refused call leaves the setting as it was.  Legal before or after weights are loaded; the setting is context
+ * state like the weights -- no part of a snapshot or of tg_config.  The staging buffers (the transformed rows and the forward's
+ * outputs, sized by the network's rows_cap) are allocated by the first evaluation under a mode other than TG_SYM_NONE;
+ * tg_net_symmetry_staging reports their bytes (0 until then). */
+#define TG_SYM_NONE 0
+#define TG_SYM_FIXED 1
+#define TG_SYM_POSITION 2
+#define TG_SYM_MEAN8 3
+int tg_net_set_symmetry(tg_ctx* ctx, int mode, uint32_t arg);   /* mode 0..3; arg = s for mode 1, seed for mode 2, else 0 */
+int tg_net_get_symmetry(tg_ctx* ctx, int* mode, uint32_t* arg);
+int tg_net_symmetry_staging(tg_ctx* ctx, uint64_t* bytes);
+/* HIP-event timing of the two symmetry kernels (bit-plane transform, output back-map) on the context's stream: enable, run, read
+ * the totals since the enable; launches that found the event pool full are left out. */
+int tg_prof_enable_symmetry(tg_ctx* ctx, int on, int max_launches);
+int tg_prof_read_symmetry(tg_ctx* ctx, double* transform_ms, double* backmap_ms, int64_t* launches);
 /* How the loaded network carries its f32 residual stream: one_stream = 1 for the DMA-fed f32 chain, which keeps ONE slice-major
  * stream between conv layers and activates it on load, 0 for every other chain; act_copy = 1 while the buffer of the pre-activated
  * copy is allocated (the DMA-fed chain with an attention layer in front of a residual block).  Either may be NULL. */

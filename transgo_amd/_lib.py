@@ -78,6 +78,11 @@ SIGNATURES = {
     "tg_net_load_async_dev": (ctypes.c_int, [_vp, ctypes.c_char_p, _vp, ctypes.c_size_t]),
     "tg_net_load_poll": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "tg_net_predict": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, _vp]),
+    "tg_net_set_symmetry": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_uint32]),
+    "tg_net_get_symmetry": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint32)]),
+    "tg_net_symmetry_staging": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
+    "tg_prof_enable_symmetry": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
+    "tg_prof_read_symmetry": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
     "tg_net_range": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_float)]),
     "tg_net_stream_layout": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "tg_prof_enable": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),

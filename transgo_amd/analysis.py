@@ -19,7 +19,7 @@ def vertex(action, board_size):
     return f"{_COLUMNS[action % S]}{S - action // S}"
 
 
-def analyse(engine, states, num_simulation=0, depth=16):
+def analyse(engine, states, num_simulation=0, depth=16, symmetry=None):
     """Search every position of `states` ([N, state_size] uint8 blobs of transgo_amd.environment.GoEnv) in evaluation mode -- a
     fresh root, no root noise, as select_action's prologue (self_play.py:689-700) -- and read the trees out.  The engine's games
     are re-rooted (`reset_from`), so whatever they held is gone; the engine must have been `reset` once before (that seeds the
@@ -31,10 +31,19 @@ def analyse(engine, states, num_simulation=0, depth=16):
       legal   bool[A]     the move is a child of the root    status  ROOT_* of SelfPlayEngine (0 = searched)
       root_value  float   w / (n + 1) of the root, from the side to move (NaN unless status is 0)
       pv      list of actions, most-visited child at each level (ties: lowest action), at most `depth`; pv_visits their visits
+    symmetry: "none" | "position" | "mean8" | an int s (transgo_amd.symmetry) evaluates under that mode for this call only; the
+    engine's own mode is put back afterwards, also when the search raises.  None = the engine's own.
     """
     states = np.ascontiguousarray(states, np.uint8)
     if states.ndim != 2:
         raise ValueError("states must be [N, state_size]")
+    if symmetry is not None:
+        old = engine.get_symmetry()
+        engine.set_symmetry(symmetry, old[1] if symmetry == "position" and old[0] == 2 else 0)
+        try:
+            return analyse(engine, states, num_simulation, depth)
+        finally:
+            engine.set_symmetry(("none", "fixed", "position", "mean8")[old[0]], old[1])
     G, N = engine.G, states.shape[0]
     out = []
     for lo in range(0, N, G):
@@ -58,6 +67,36 @@ def analyse(engine, states, num_simulation=0, depth=16):
             out.append(dict(visits=n.copy(), prior=rc["prior"][g].copy(), q=q, legal=present, status=int(rc["status"][g]),
                             root_value=root_value, pv=[int(a) for a in act[g, :m]], pv_visits=[int(v) for v in vis[g, :m]]))
     return out
+
+
+def symmetry_spread(net, states):
+    """How far a weight set is from equivariance: every position of `states` ([N, state_size] blobs) evaluated by `net` (a
+    transgo_amd.model.HipNetwork of the same board size and planes) under each of the eight symmetries (mode "fixed", s = 0..7),
+    outputs mapped back to the position's own orientation.  One dict per position: "policy" / "value" = the largest absolute
+    difference between any two of the eight policies / values (0 = the network gives one answer in every orientation).  The
+    network's own mode is put back afterwards."""
+    import ctypes
+    states = np.ascontiguousarray(states, np.uint8)
+    if states.ndim != 2:
+        raise ValueError("states must be [N, state_size]")
+    N = states.shape[0]
+    if N == 0:
+        return []
+    obs = np.zeros((N, net.C, net.S, net.S), np.float32)
+    net.ctx.call("tg_env_query", states.ctypes.data_as(ctypes.c_void_p), N, None, None, obs.ctypes.data_as(ctypes.c_void_p),
+                 None, None, None, None, None)
+    old = net.get_symmetry()
+    try:
+        pols, vals = [], []
+        for s in range(8):
+            net.set_symmetry(s)
+            p, v, _ = net.main_prediction(obs)
+            pols.append(p); vals.append(v.reshape(N))
+    finally:
+        net.set_symmetry(("none", "fixed", "position", "mean8")[old[0]], old[1])
+    pols, vals = np.stack(pols), np.stack(vals)
+    return [dict(policy=float((pols[:, i].max(0) - pols[:, i].min(0)).max()), value=float(vals[:, i].max() - vals[:, i].min()))
+            for i in range(N)]
 
 
 def playout_ownership(env, states, playouts=64, seed=0):

@@ -30,6 +30,9 @@ class Config:
                                                  # filters, and network = "transgo" at 9x9 with 128 filters, not at 19x19); "f16r" (attention-free
                                                  # towers only): the residual stream in fp16 as well (+4-6 %, error < 4e-4 over 40 blocks);
                                                  # "f32x3": split precision -- conv operands as fp16 hi + lo, f32 accumulate, ~1e-6 of f32
+        self.eval_symmetry = "none"              # "position": every evaluation in one orientation chosen from (symmetry_seed, position);
+                                                 # "mean8": the mean over all eight (match play, analysis); transgo_amd/symmetry.py.
+        self.symmetry_seed = 0                   # Only "none" keeps bit parity with the reference's self-play
         self.batch_size = 2048
         self.train_play_ratio = 7500 / 100000    # configure.py:61
         self.adjust_train_play_ratio = True

@@ -141,6 +141,7 @@ void tg_destroy(tg_ctx* ctx) {
     (void)hipSetDevice(ctx->cfg.device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     tg_engine_destroy(ctx);
+    ctx->sym.release();
     ctx->env_in.release(); ctx->env_out.release(); ctx->env_act.release(); ctx->env_flags.release();
     ctx->env_u8.release(); ctx->env_f32.release(); ctx->env_i32.release(); ctx->env_rng.release(); ctx->env_moves.release();
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);

@@ -2312,6 +2312,41 @@ int forward(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, floa
     TG_FAIL(ctx, TG_ERR_ARG, "unsupported (board_size, net_filters): built are 9x{32,64,128,256}, 19x{128,256}");
 }
 
+// forward() under the context's symmetry mode (tg_net_set_symmetry; symmetry.hip) -- the one place tg_net_forward (bit input
+// through the engine's slot table) and tg_net_predict (float planes) reach the network.  Mode 0 is forward() itself: nothing else
+// is launched or allocated.  Otherwise the rows are transformed into a dense staging batch, the unchanged forward reads it through
+// in_bits / in_slot and writes to staging, and the back-map kernel puts the outputs into policy / value / own in the original
+// orientation; mean8 does that for s = 0..7 in order, accumulating in the destination.  No weight refresh is adopted in here
+// (adopt_pending is the callers'), so the eight passes of one mean8 evaluation see one weight set.
+int forward_sym(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, float* value, float* own) {
+    SymState& y = ctx->sym;
+    if (y.mode == SYM_NONE) return forward(ctx, n, obs, rows, policy, value, own);
+    if (rows <= 0) return TG_OK;
+    if (rows > n->rows_cap) TG_FAIL(ctx, TG_ERR_ARG, "network batch larger than the allocated activation buffers");
+    const int W = (n->C * n->P + 31) / 32;
+    const bool from_planes = n->in_bits == nullptr;
+    { int rc = sym_reserve(ctx, n->rows_cap, W, n->A, n->P, from_planes); if (rc) return rc; }
+    const uint32_t* src = n->in_bits; const int32_t* slot = n->in_slot;
+    if (from_planes) {
+        int rc = sym_pack(ctx, obs, rows, n->C, n->P, W); if (rc) return rc;
+        src = (const uint32_t*)y.packed.p; slot = nullptr;
+    }
+    const uint32_t* keep_bits = n->in_bits; const int32_t* keep_slot = n->in_slot; const int keep_words = n->in_words;
+    const int passes = y.mode == SYM_MEAN8 ? 8 : 1;
+    int rc = TG_OK;
+    for (int k = 0; k < passes && rc == TG_OK; ++k) {
+        rc = y.mode == SYM_MEAN8 ? sym_transform(ctx, src, slot, rows, n->S, n->C, W, SYM_FIXED, (uint32_t)k)
+                                 : sym_transform(ctx, src, slot, rows, n->S, n->C, W, y.mode, y.arg);
+        if (rc) break;
+        n->in_bits = (const uint32_t*)y.bits.p; n->in_slot = (const int32_t*)y.ident.p; n->in_words = W;
+        rc = forward(ctx, n, nullptr, rows, (float*)y.pol.p, (float*)y.val.p, own ? (float*)y.own.p : nullptr);
+        n->in_bits = keep_bits; n->in_slot = keep_slot; n->in_words = keep_words;
+        if (rc) break;
+        rc = sym_backmap(ctx, policy, value, own, rows, n->S, passes == 1 ? 0 : k == 0 ? 0 : k == 7 ? 2 : 1);
+    }
+    return rc;
+}
+
 // arch: one letter per trunk layer, 'R' residual block / 'A' Self_Attention block, optional "+P" = attention in the policy
 // head.  The reference MainNetwork (model.py:49-76) is "RARRRARRRRAR+P"; BASELINE's N-block tower is N x 'R'.
 bool parse_arch(const std::string& arch, std::string* trunk, bool* pol) {
@@ -2726,7 +2761,7 @@ int tg_net_forward(tg_ctx* ctx, int rows) {
     if (!e || !e->net) TG_FAIL(ctx, TG_ERR_STATE, "no network weights loaded (tg_net_load)");
     Net* n = e->net;
     n->in_bits = e->dev.obs_bits; n->in_slot = e->dev.row_slot; n->in_words = e->dev.obs_words;
-    const int rc = forward(ctx, n, nullptr, rows, e->dev.policy, e->dev.value, nullptr);
+    const int rc = forward_sym(ctx, n, nullptr, rows, e->dev.policy, e->dev.value, nullptr);
     n->in_bits = nullptr; n->in_slot = nullptr;
     return rc;
 }
@@ -2746,7 +2781,7 @@ int tg_net_predict(tg_ctx* ctx, const float* obs, int n_rows, float* policy, flo
             TG_FAIL(ctx, TG_ERR_HIP, "hipMalloc failed (predict scratch)");
         float* d_pol = (float*)dout.p; float* d_val = d_pol + (size_t)k * A;
         TG_HIP(ctx, hipMemcpyAsync(din.p, obs + (size_t)done * C * P, sizeof(float) * k * C * P, hipMemcpyHostToDevice, ctx->stream));
-        int rc = forward(ctx, n, (const float*)din.p, k, d_pol, d_val, own ? n->own : nullptr);
+        int rc = forward_sym(ctx, n, (const float*)din.p, k, d_pol, d_val, own ? n->own : nullptr);
         if (rc) return rc;
         TG_HIP(ctx, hipMemcpyAsync(policy + (size_t)done * A, d_pol, sizeof(float) * k * A, hipMemcpyDeviceToHost, ctx->stream));
         TG_HIP(ctx, hipMemcpyAsync(value + done, d_val, sizeof(float) * k, hipMemcpyDeviceToHost, ctx->stream));

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "sym_dev.h"
 
 namespace {
 
@@ -22,21 +23,7 @@ struct Replay {
     tg::DevBuf idx, o_state, o_pi, o_z, o_own, stage;
 };
 
-// symmetry s = 2*(i-1) + f for the reference's loop "for i in 1..4: rot90(x, i); then fliplr of that" (self_play.py:944-965).
-// Returns the SOURCE point of destination (r, c).  np.rot90(m, k)[r][c]: k=1: m[c][S-1-r]; k=2: m[S-1-r][S-1-c];
-// k=3: m[S-1-c][r]; k=4: m[r][c].  fliplr(y)[r][c] = y[r][S-1-c].
-__device__ __forceinline__ int sym_src(int s, int r, int c, int S) {
-    const int k = (s >> 1) + 1, f = s & 1;
-    if (f) c = S - 1 - c;
-    int rr, cc;
-    switch (k & 3) {
-        case 1: rr = c; cc = S - 1 - r; break;
-        case 2: rr = S - 1 - r; cc = S - 1 - c; break;
-        case 3: rr = S - 1 - c; cc = r; break;
-        default: rr = r; cc = c; break;
-    }
-    return rr * S + cc;
-}
+using tg::sym_src;                   // sym_dev.h: source point of destination (r, c) under symmetry s
 
 __global__ __launch_bounds__(256) void k_sample(const uint32_t* __restrict__ obs, const int32_t* __restrict__ counts,
                                                 const float* __restrict__ z, const int8_t* __restrict__ own,

@@ -13,6 +13,7 @@ import time
 import numpy as np
 
 from . import _lib
+from . import symmetry as _symmetry
 
 
 def _ptr(a):
@@ -100,7 +101,8 @@ def choose_moves_batch(visits, steps, u, live, selfplay=True):
 class SelfPlayEngine:
     def __init__(self, n_games, board_size=9, num_simulation=210, parallel_readouts=4, c_puct1=3, c_puct2=0.05,
                  wu_loss=2, komi=7.5, max_step=120, encode_dim=10, net_blocks=6, net_filters=128, arena_slots=0,
-                 device=0, evaluator=None, net_precision="f32", record_games=True, pool_slots=0):
+                 device=0, evaluator=None, net_precision="f32", record_games=True, pool_slots=0, eval_symmetry="none",
+                 symmetry_seed=0):
         cfg = _lib.default_config()
         cfg.record_games = 1 if record_games else 0       # per-move records in HBM for tg_sp_harvest (self-play); evaluation matches need none
         cfg.net_precision = {"f32": 0, "f16": 1, "f16r": 2, "f32x3": 3}[net_precision]
@@ -118,9 +120,31 @@ class SelfPlayEngine:
         self.errored = np.zeros(n_games, bool)       # slots parked by a tree-arena overflow (restart them with reset(mask))
         self.device = device
         self.begin_move_s = 0.0                      # wall clock spent in tg_sp_begin_move (root noise on the host), for bench.py
+        self._host_symmetry = (0, 0)
+        if _symmetry.parse_mode(eval_symmetry, symmetry_seed)[0] != 0:
+            self.set_symmetry(eval_symmetry, symmetry_seed)
 
     def close(self):
         self.ctx.close()
+
+    def set_symmetry(self, mode, arg=0):
+        """Symmetry-aware evaluation (transgo_amd.symmetry): "none" | "position" | "mean8" or an int s = 0..7; arg = the seed of
+        "position".  With the network on the GPU this sets the context's mode (tg_net_set_symmetry); a host `evaluator` is
+        wrapped with symmetry.evaluate_with_symmetry, so both kinds of engine mean the same thing.  Legal at a move boundary
+        only (no evaluation batch pending)."""
+        m, a = _symmetry.parse_mode(mode, arg)
+        if self.evaluator is None:
+            self.ctx.call("tg_net_set_symmetry", m, a)
+        else:
+            self._host_symmetry = (m, a)
+
+    def get_symmetry(self):
+        """(mode number 0..3, arg) in force: the context's (tg_net_get_symmetry), or the host evaluator's wrapper's."""
+        if self.evaluator is not None:
+            return self._host_symmetry
+        m, a = ctypes.c_int(), ctypes.c_uint32()
+        self.ctx.call("tg_net_get_symmetry", ctypes.byref(m), ctypes.byref(a))
+        return int(m.value), int(a.value)
 
     # ---- evaluation of the pending batch --------------------------------------------------------------------------------
     def _evaluate(self, rows=None):
@@ -135,7 +159,9 @@ class SelfPlayEngine:
             return
         obs = np.empty((rows, self.C, self.S, self.S), np.float32)
         self.ctx.call("tg_sp_batch_obs", _ptr(obs), rows)
-        policy, value = self.evaluator(obs)
+        m, a = self._host_symmetry
+        policy, value = (self.evaluator(obs) if m == 0 else
+                         _symmetry.evaluate_with_symmetry(self.evaluator, obs, ("none", "fixed", "position", "mean8")[m], a))[:2]
         policy = np.ascontiguousarray(policy, np.float32); value = np.ascontiguousarray(value, np.float32).reshape(-1)
         assert policy.shape == (rows, self.A) and value.shape == (rows,)
         self.ctx.call("tg_sp_set_eval", _ptr(policy), _ptr(value), rows)

@@ -200,6 +200,26 @@ class HipNetwork:
         self.ctx.call("tg_net_range", ctypes.byref(n), ctypes.byref(w))
         return {"fp16_overflows": int(n.value), "weight_absmax": float(w.value)}
 
+    def set_symmetry(self, mode, arg=0):
+        """Symmetry-aware evaluation (transgo_amd.symmetry; tg_net_set_symmetry): "none" | "position" | "mean8" or an int s = 0..7
+        (every row under s); arg = the seed of "position".  main_prediction honours it from the next call on; legal before or
+        after set_weights."""
+        from . import symmetry
+        m, a = symmetry.parse_mode(mode, arg)
+        self.ctx.call("tg_net_set_symmetry", m, a)
+
+    def get_symmetry(self):
+        """(mode number 0..3, arg) in force (tg_net_get_symmetry)."""
+        m, a = ctypes.c_int(), ctypes.c_uint32()
+        self.ctx.call("tg_net_get_symmetry", ctypes.byref(m), ctypes.byref(a))
+        return int(m.value), int(a.value)
+
+    def symmetry_staging_bytes(self):
+        """Bytes of symmetry staging buffers the context holds: 0 until an evaluation ran under a mode other than "none"."""
+        n = ctypes.c_uint64()
+        self.ctx.call("tg_net_symmetry_staging", ctypes.byref(n))
+        return int(n.value)
+
     def get_weights(self):                               # model.py:23-24
         return self._weights
 

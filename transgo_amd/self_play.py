@@ -93,7 +93,8 @@ class BatchedSelfPlay:
             encode_dim=config.encode_state_channels, net_blocks=self.blocks, net_filters=self.filters,
             arena_slots=arena_slots, device=device, evaluator=evaluator,
             pool_slots=pool_slots or getattr(config, "tree_pool_slots", 0),
-            net_precision=getattr(config, "inference_dtype", "f32"))
+            net_precision=getattr(config, "inference_dtype", "f32"),
+            eval_symmetry=getattr(config, "eval_symmetry", "none"), symmetry_seed=getattr(config, "symmetry_seed", 0))
         self.seed_fn = seed_fn
         self.games_started = np.zeros(n_games, np.int64)
         self.seeds = np.zeros(n_games, np.uint32)          # seed of the game now running in each slot
@@ -613,7 +614,7 @@ class SelfPlay:
             c_puct1=cfg.c_puct1, c_puct2=cfg.c_puct2, wu_loss=cfg.wu_loss, komi=cfg.komi, max_step=cfg.max_step,
             encode_dim=cfg.encode_state_channels, net_blocks=w.blocks, net_filters=w.filters, device=w.device,
             net_precision=getattr(cfg, "inference_dtype", "f32"), evaluator=evaluators[who] if evaluators else None,
-            record_games=False)
+            record_games=False, eval_symmetry=getattr(cfg, "eval_symmetry", "none"), symmetry_seed=getattr(cfg, "symmetry_seed", 0))
         eng = {"train": mk("train"), "eval": mk("eval")}
         if not evaluators:
             for who, key in (("train", "weights"), ("eval", "evaluate_weights")):
@@ -696,7 +697,8 @@ class SelfPlay:
             n_games, board_size=cfg.board_size, num_simulation=cfg.num_simulation, parallel_readouts=cfg.parallel_readouts,
             c_puct1=cfg.c_puct1, c_puct2=cfg.c_puct2, wu_loss=cfg.wu_loss, komi=cfg.komi, max_step=cfg.max_step,
             encode_dim=cfg.encode_state_channels, net_blocks=w.blocks, net_filters=w.filters, device=w.device,
-            net_precision=getattr(cfg, "inference_dtype", "f32"), evaluator=fn, record_games=False)
+            net_precision=getattr(cfg, "inference_dtype", "f32"), evaluator=fn, record_games=False,
+            eval_symmetry=getattr(cfg, "eval_symmetry", "none"), symmetry_seed=getattr(cfg, "symmetry_seed", 0))
         try:
             if fn is None:
                 arch = w.arch
