@@ -1,6 +1,6 @@
 #!/bin/bash
 # Run ON THE GPU BOX (gpurun): regenerates the summaries committed under profiles/ for the current round.
-#   scripts/collect_profiles.sh <tag> <section> [<section> ...]      sections: default x3 transgo att tree
+#   scripts/collect_profiles.sh <tag> <section> [<section> ...]      sections: default default_traffic default_trace default_sq x3 transgo att tree
 # rocprofv3 wraps `python3 bench.py --no-launcher --no-cpu-baseline ...` directly (the profiled process is the rank itself: a process
 # whose GPU the profiler has already initialised must not start GPU children).  Counters (--pmc) are collected in their own passes
 # with --kernel-trace only.  Raw output stays on the box under /tmp; the summaries land in gpurun_out/prof_<tag>/.
@@ -30,6 +30,14 @@ for sec in "$@"; do
     trace bench --steps 20 --warmup 5 || exit 1
     pmc fetch FETCH_SIZE -- --steps 1 --warmup 1 && pmc write WRITE_SIZE -- --steps 1 --warmup 1 || exit 1
     python3 scripts/pmc_json.py $RAW $OUT/pmc_traffic.json > $OUT/pmc_traffic.txt 2>&1; say "default pmc done" ;;
+  default_traffic)   # the traffic counters alone
+    pmc fetch FETCH_SIZE -- --steps 1 --warmup 1 && pmc write WRITE_SIZE -- --steps 1 --warmup 1 || exit 1
+    python3 scripts/pmc_json.py $RAW $OUT/pmc_traffic.json > $OUT/pmc_traffic.txt 2>&1; say "default traffic done" ;;
+  default_trace)   # the kernel times alone
+    trace bench --steps 20 --warmup 5 || exit 1 ;;
+  default_sq)   # MFMA-busy fraction of the conv kernels: busy cycles / (GRBM_GUI_ACTIVE x 128), medians = the full-batch launches
+    pmc sq SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE -- --steps 1 --warmup 1 || exit 1
+    python3 scripts/pmc_summary.py $RAW/sq k_conv3x3_sg > $OUT/pmc_sq.txt; say "default sq done" ;;
   x3)        # the same workload under the split-precision network
     trace x3 --dtype f32x3 --steps 6 --warmup 2 || exit 1
     pmc x3_sq $SQ -- --dtype f32x3 --steps 1 --warmup 1 && pmc x3_fetch FETCH_SIZE -- --dtype f32x3 --steps 1 --warmup 1 && pmc x3_write WRITE_SIZE -- --dtype f32x3 --steps 1 --warmup 1 || exit 1

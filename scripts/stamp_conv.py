@@ -31,7 +31,8 @@ s = np.array([int(v) for v in out], dtype=np.int64).reshape(2, 2, 3, 8)         
 print(f"rows {B}, blocks {NB}; stamped build: "
       f"{n.value} conv launches, {ms.value / n.value:.3f} ms on average (not the product's time)")
 names = ["entry -> bias (|s2|t2) issued", "-> weight DMAs of the prologue issued", "-> first counted wait + barrier passed",
-         "-> first MFMAs issued (B fragments, residual landed)", "-> end of the walk", "-> epilogue: every store issued", "-> stores written"]
+         "-> first MFMAs issued (B fragments, residual landed)", "-> last MFMA issued (all stores but the last tile's are out)",
+         "-> the last cout tile's stores issued", "-> stores written"]
 for e, kern in enumerate(("conv1 <9,128,0,SIN>", "conv2 <9,128,1,SIN,SOUT>")):
     for r, rnd in enumerate(("first round (range 0)", "middle round (range 7)")):
         print(f"{kern}, {rnd}: ticks per phase (share of the workgroup) for interior | edge | corner")

@@ -426,8 +426,8 @@ __device__ __forceinline__ int swz64(int row) { return ((row >> 2) & 1) << 1; }
 // MFMA column depends on its own B column only.  The buffer resource ends with the padded tensor, so nothing is read past it.
 // Workgroups are numbered board range major, and inside a range longest walk first (conv_pos_of): the 81 (361) workgroups that
 // share one range's input are neighbours, and each XCD takes a contiguous run of them.
-// F = 128: 95 VGPRs (96 with SOUT, 104 with the activation on load) and 34 KB of LDS, four workgroups per CU; F = 256: 159 VGPRs (168
-// in the activating kernel only) and 67 KB, two per CU.  Three tiles per wave
+// F = 128: 98 VGPRs (106 with the activation on load, 110 with a row-major residual) and 34 KB of LDS, four workgroups per CU;
+// F = 256: 162 VGPRs (170 / 206) and 67 KB, two per CU.  Three tiles per wave
 // (192 boards, three workgroups per CU at F = 128), the better shape of the row-ordered kernel on full rounds, measured 4-7 %
 // slower here at 9x9 and 19x19: the walks differ in length, and four shorter waves per SIMD fill each other's gaps better.
 // The fixed part of a workgroup, what it pays before its first MFMA:
@@ -442,6 +442,8 @@ __device__ __forceinline__ int swz64(int row) { return ((row >> 2) & 1) << 1; }
 //  * without the activation on load the hand-over b_cur = b_next goes through an empty asm at the END of the stage, as act_b does
 //    with VALU: the compiler cannot fold the copy into the next stage's MFMA operands, so its own vmcnt(0) for the fragments
 //    lands there, a stage after their load, and not in front of the next stage's first MFMA, a few instructions after the next load.
+// The tail of a workgroup: the last pair of stages is peeled off the loop and closed by no barrier, and the last stage carries the
+// epilogue between its MFMAs, a cout tile behind them (see there): a wave ends two stores after its last MFMA.
 // -DTG_CONV_STAMP (diagnostic build only, scripts/stamp_conv.py): phase stamps of wave 0 of six workgroups at 9x9 / F = 128.
 #ifdef TG_CONV_STAMP
 __device__ unsigned long long g_conv_stamp[2 * 6 * 8];                  // [EPI][interior, edge, corner of range 0 | of range 7][phase]
@@ -610,57 +612,106 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
     }
     dma_w(2); dma_w(3);
 
+    // One stage of the walk but the last: stage k's MFMAs under the loads of stage k + 1's fragments.
+    auto walk_stage = [&](int k) {
+        const float* wcur = ws[k & (D - 1)];
+        load_b(b_next, k + 1);
+        __builtin_amdgcn_sched_barrier(0);                               // keep the loads HERE: hipcc sinks them to their use, a stage later
+        f32x4 a_cur = *reinterpret_cast<const f32x4*>(wcur + aoff);
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) {
+            f32x4 a_next = a_cur;
+            if (ct + 1 < CT) a_next = *reinterpret_cast<const f32x4*>(wcur + (ct + 1) * 256 + aoff);
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4)
+#pragma unroll
+                for (int t = 0; t < NPT; ++t)
+                    acc[ct][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[s4], b_cur[t][s4], acc[ct][t], 0, 0, 0);
+            a_cur = a_next;
+#ifdef TG_CONV_STAMP
+            if (ct == 0 && k == 0) TG_CSTAMP(4);                         // the first MFMAs have issued: their operands had landed
+#endif
+        }
+        if constexpr (ACT) {
+            __builtin_amdgcn_sched_barrier(0);                           // behind the stage's MFMAs: the fragments are a stage old here
+            act_b(b_cur, b_next);
+        } else {
+            __builtin_amdgcn_sched_barrier(0);                           // the same place for the fragments' wait
+#pragma unroll
+            for (int t = 0; t < NPT; ++t) {
+                asm volatile("" : "+v"(b_next[t]));
+                b_cur[t] = b_next[t];
+            }
+        }
+    };
 #pragma unroll 1
-    for (int k0 = 0; k0 < nst; k0 += 2) {
+    for (int k0 = 0; k0 < nst - 2; k0 += 2) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const int k = k0 + h;
-            if (active) {
-                const float* wcur = ws[k & (D - 1)];
-                if (k + 1 < nst) load_b(b_next, k + 1);
-                __builtin_amdgcn_sched_barrier(0);                       // keep the loads HERE: hipcc sinks them to their use, a stage later
-                f32x4 a_cur = *reinterpret_cast<const f32x4*>(wcur + aoff);
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct) {
-                    f32x4 a_next = a_cur;
-                    if (ct + 1 < CT) a_next = *reinterpret_cast<const f32x4*>(wcur + (ct + 1) * 256 + aoff);
-#pragma unroll
-                    for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-                        for (int t = 0; t < NPT; ++t)
-                            acc[ct][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[s4], b_cur[t][s4], acc[ct][t], 0, 0, 0);
-                    a_cur = a_next;
-#ifdef TG_CONV_STAMP
-                    if (ct == 0 && k == 0) TG_CSTAMP(4);                 // the first MFMAs have issued: their operands had landed
-#endif
-                }
-                if constexpr (ACT) {
-                    __builtin_amdgcn_sched_barrier(0);                   // behind the stage's MFMAs: the fragments are a stage old here
-                    act_b(b_cur, b_next);
-                } else {
-                    __builtin_amdgcn_sched_barrier(0);                   // the same place for the fragments' wait
-#pragma unroll
-                    for (int t = 0; t < NPT; ++t) {
-                        asm volatile("" : "+v"(b_next[t]));
-                        b_cur[t] = b_next[t];
-                    }
-                }
-            }
+            if (active) walk_stage(k0 + h);
             TG_VMCNT(0);                                                 // B fragments of stage k+1 (and any weight pieces): a stage old
         }
         TG_BARRIER();                                                    // the next pair has landed for everybody; this pair's slots are free
         if (k0 + 4 < nst) { dma_w(k0 + 4); dma_w(k0 + 5); }
     }
-    TG_CSTAMP(5);
+    // The last pair (nst is even) is peeled.  It landed before the barrier above, no DMA follows and nobody writes the ring or `par`
+    // again, so no barrier closes it: a wave goes from its last MFMAs to its stores and ends without waiting for the slowest one.
     if (!active) return;
-    int mrow[NPT], srow[NPT];
+    walk_stage(nst - 2);
+    TG_VMCNT(0);
+    // The last stage with the epilogue inside it.  acc[ct][.] is final once cout tile ct's 4 * NPT MFMAs have issued: bias (ReLU for
+    // EPI 0; EPI 1 started from the residual) and the 16-B store of tile ct go out behind the first NPT MFMAs of tile ct + 1, whose
+    // issue covers the results' latency, and only the last tile's NPT stores stand behind the last MFMA.  Per element the same terms
+    // in the same order as a walk followed by conv_epilogue, and the same expressions behind them.  Buffer stores: the whole address
+    // is a 32-bit byte offset (the lane's row + the cout tile), and a board past the batch carries an offset past the tensor, which
+    // the range check drops -- no branch between the MFMAs.  `out2` is always null on this kernel and is left out here.
+    constexpr bool SM = EPI == 0 || SOUT;                                // `out` slice-major in the conv's row order, else row-major
+    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(out, 0, (SM ? Msm : M) * F * 4, 0x00020000);
+    const unsigned ostep = SM ? (unsigned)Msm * (CC * 4) : CC * 4;       // bytes from one cout tile to the next
+    unsigned ooff[NPT];
 #pragma unroll
     for (int t = 0; t < NPT; ++t) {
         const int b = (grp0 + t) * 16 + j;
-        mrow[t] = b < rows ? b * P + p : M;                              // M: not stored
-        srow[t] = conv_sg_row(b, p, P);
+        ooff[t] = b >= rows ? 0x80000000u : SM ? (unsigned)(conv_sg_row(b, p, P) * CC + kq * 4) * 4 : (unsigned)((b * P + p) * F + kq * 4) * 4;
     }
-    conv_epilogue<F, CT, NPT, (EPI == 1 ? 2 : EPI), EPI == 0 || SOUT, true>(acc, mrow, M, 0, kq, out, res, out2, par, srow, Msm);
+    auto store_tile = [&](int ct, f32x4 bv) {
+#pragma unroll
+        for (int t = 0; t < NPT; ++t) {
+            f32x4 v = acc[ct][t] + bv;
+            if constexpr (EPI == 0) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+            }
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rout, (int)(ooff[t] + (unsigned)ct * ostep), 0, 0);
+        }
+    };
+    {
+        const float* wcur = ws[(nst - 1) & (D - 1)];
+        const float* pb = par + kq * 4;
+        __builtin_amdgcn_sched_barrier(0);                               // the offsets above are computed in front of the stage
+        f32x4 a_cur = *reinterpret_cast<const f32x4*>(wcur + aoff);
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) {
+            f32x4 a_next = a_cur, bv = a_cur;
+            if (ct + 1 < CT) a_next = *reinterpret_cast<const f32x4*>(wcur + (ct + 1) * 256 + aoff);
+            if (ct > 0) bv = *reinterpret_cast<const f32x4*>(pb + (ct - 1) * 16);   // read here, used two MFMAs on
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+#pragma unroll
+                for (int t = 0; t < NPT; ++t)
+                    acc[ct][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[s4], b_cur[t][s4], acc[ct][t], 0, 0, 0);
+                if (s4 == 0 && ct > 0) {                                 // hipcc sinks stores to the end: keep tile ct - 1's HERE
+                    __builtin_amdgcn_sched_barrier(0);
+                    store_tile(ct - 1, bv);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            a_cur = a_next;
+        }
+        TG_CSTAMP(5);                                                    // the last MFMA has issued
+        __builtin_amdgcn_sched_barrier(0);
+        store_tile(CT - 1, *reinterpret_cast<const f32x4*>(pb + (CT - 1) * 16));
+    }
 #ifdef TG_CONV_STAMP
     TG_CSTAMP(6);                                                        // every store issued
     TG_VMCNT(0);
