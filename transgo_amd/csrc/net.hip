@@ -424,8 +424,11 @@ __device__ __forceinline__ int swz64(int row) { return ((row >> 2) & 1) << 1; }
 // Boards past the batch: a wave none of whose groups exists skips its loads and MFMAs (it still feeds the weight ring and meets
 // the barriers); absent boards next to present ones are computed on whatever their never-written rows hold and never stored -- an
 // MFMA column depends on its own B column only.  The buffer resource ends with the padded tensor, so nothing is read past it.
-// Workgroups are numbered board range major, and inside a range longest walk first (conv_pos_of): the 81 (361) workgroups that
-// share one range's input are neighbours, and each XCD takes a contiguous run of them.
+// Workgroups are numbered per XCD (workgroup b runs on XCD b % 8 and is the (b >> 3)-th of its list, conv_launch_wg in conv_rows.h):
+// an XCD takes whole board ranges, range-major and inside a range longest walk first (conv_pos_of), so the 81 (361) workgroups that
+// share one range's input are neighbours on one L2 -- but its last K ranges and its share of the nrange % 8 leftover ranges are
+// spent CLASS-major, every interior position, then every edge, then every corner: each XCD ends on its shortest walks, so fewer slots
+// stand empty while the last workgroups finish (the order changes nothing that a workgroup computes).
 // F = 128: 98 VGPRs (106 with the activation on load, 110 with a row-major residual) and 34 KB of LDS, four workgroups per CU;
 // F = 256: 162 VGPRs (170 / 206) and 67 KB, two per CU.  Three tiles per wave
 // (192 boards, three workgroups per CU at F = 128), the better shape of the row-ordered kernel on full rounds, measured 4-7 %
@@ -445,13 +448,21 @@ __device__ __forceinline__ int swz64(int row) { return ((row >> 2) & 1) << 1; }
 // The tail of a workgroup: the last pair of stages is peeled off the loop and closed by no barrier, and the last stage carries the
 // epilogue between its MFMAs, a cout tile behind them (see there): a wave ends two stores after its last MFMA.
 // -DTG_CONV_STAMP (diagnostic build only, scripts/stamp_conv.py): phase stamps of wave 0 of six workgroups at 9x9 / F = 128.
+// It also records how a launch DRAINS (stamp_conv.py --drain): lane 0 of wave 0 of EVERY workgroup of the last conv1 /
+// stream-to-stream conv2 launch leaves its entry and its end (every store issued) on the cycle counter and on the device-wide 100 MHz
+// clock, its (range, p) and the XCD / CU it ran on, indexed by blockIdx.x.
 #ifdef TG_CONV_STAMP
 __device__ unsigned long long g_conv_stamp[2 * 6 * 8];                  // [EPI][interior, edge, corner of range 0 | of range 7][phase]
+constexpr int TG_DRAIN_CAP = 16384, TG_DRAIN_REC = 6;                   // workgroups of a launch that are recorded, words per record
+__device__ unsigned long long g_conv_drain[2 * TG_DRAIN_CAP * TG_DRAIN_REC];   // [EPI][blockIdx.x][entry, end, entry rt, end rt, range | p, xcc | hw_id]
 #define TG_CSTAMP(i) do { __builtin_amdgcn_sched_barrier(0); if (cslot >= 0 && lane == 0) g_conv_stamp[cslot * 8 + (i)] = __builtin_readcyclecounter(); \
                           __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
 #define TG_CSTAMP(i) do { } while (0)
 #endif
+// K of conv_launch_wg: the ranges per XCD that are spent class-major, from {1, 2, 4} (the runs that decided it: DESIGN.md 8.12).
+// It lives here and not in conv_rows.h so that the source hash the committed traffic counters are keyed on covers it.
+constexpr int conv_drain_k(int S, int F) { return S == 9 && (F == 128 || F == 256) ? 4 : 1; }
 template <int S, int F, int EPI, bool SIN = false, bool SOUT = false>
 __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const float* __restrict__ in, float* __restrict__ out,
                                                                        const float* __restrict__ res, const float* __restrict__ Ws,
@@ -462,34 +473,42 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
     constexpr int WPW = CT / 4;
     constexpr int NSL = F / CC, D = 4;                                  // two stages per barrier, two pairs resident
     static_assert((F == 128 || F == 256) && NSL % 2 == 0, "tile geometry");
+    static_assert(conv_drain_k(S, F) == 1 || conv_drain_k(S, F) == 2 || conv_drain_k(S, F) == 4, "the K that tests/test_conv_launch_order.py checks");
     __shared__ __attribute__((aligned(16))) float ws[D][F * CC];
     __shared__ __attribute__((aligned(16))) float par[3 * F];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 15, kq = lane >> 4;
 #ifdef TG_CONV_STAMP
-    const unsigned long long t_entry = __builtin_readcyclecounter();
+    const unsigned long long t_entry = __builtin_readcyclecounter(), rt_entry = __builtin_amdgcn_s_memrealtime();
     __builtin_amdgcn_sched_barrier(0);
+    unsigned long long* const drec = (EPI == 0 || SOUT) && tid == 0 && (int)blockIdx.x < TG_DRAIN_CAP
+                                         ? g_conv_drain + ((size_t)(EPI == 1 ? TG_DRAIN_CAP : 0) + blockIdx.x) * TG_DRAIN_REC : nullptr;
 #endif
-    // XCD-aware order: workgroup b runs on XCD b % 8, so XCD x takes the CONTIGUOUS run [x * tpx, (x + 1) * tpx) of the numbering
-    // above -- the workgroups that read one board range's input share one L2
-    const int tpx = ((int)gridDim.x + 7) >> 3;
-    const int bid = ((int)blockIdx.x & 7) * tpx + ((int)blockIdx.x >> 3);
+    // XCD-aware, drain-aware order: workgroup b runs on XCD b % 8 and is the (b >> 3)-th of that XCD's list (conv_launch_wg) --
+    // whole board ranges first, whose workgroups share one L2, and the short walks of its last ranges at the very end
     const int nrange = (rows + TB - 1) / TB;
-    if (bid >= nrange * P) return;                                      // the grid is rounded up to a multiple of 8
-    const int range = bid / P;
-    const int p = conv_pos_of(bid - range * P, S);
+    const conv_wg wg = conv_launch_wg((int)blockIdx.x & 7, (int)blockIdx.x >> 3, nrange, S, conv_drain_k(S, F));
+#ifdef TG_CONV_STAMP
+    if (drec && wg.range < 0) { drec[0] = drec[1] = t_entry; drec[2] = drec[3] = rt_entry; drec[4] = ~0ull; }
+#endif
+    if (wg.range < 0) return;                                           // the grid is 8 x the longest list
+    const int range = wg.range, p = wg.p;
     const int M = rows * P, Msm = conv_sg_rows(rows, P);
     constexpr bool ACT = EPI == 0 && SIN;                               // s2 / t2 are then the BN of `in`, applied as its fragments land
 #ifdef TG_CONV_STAMP
     // range 0 runs in the first round of XCD 0, range 7 in the middle of its run of 15; conv_pos_of: interior, edge, corner positions
     int cslot = -1;
     if (S == 9 && F == 128 && (EPI == 0 || SOUT) && wave == 0 && (range == 0 || range == 7)) {
-        const int li = bid - range * P, I = S - 2;
-        const int cls = li == 0 ? 0 : li == I * I ? 1 : li == I * I + 4 * I ? 2 : -1;
+        const int cls = p == conv_pos_of(conv_class_first(0, S), S) ? 0 : p == conv_pos_of(conv_class_first(1, S), S) ? 1
+                        : p == conv_pos_of(conv_class_first(2, S), S) ? 2 : -1;   // the first position of each class
         if (cls >= 0) cslot = (EPI == 1 ? 6 : 0) + (range == 0 ? 0 : 3) + cls;
     }
     if (cslot >= 0 && lane == 0) g_conv_stamp[cslot * 8] = t_entry;
+    if (drec) {                                                          // HW_REG_XCC_ID [3:0] and HW_REG_HW_ID (cu_id, sh_id, se_id in [15:8])
+        drec[0] = t_entry; drec[2] = rt_entry; drec[4] = (unsigned long long)range << 32 | (unsigned)p;
+        drec[5] = (unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) << 32 | __builtin_amdgcn_s_getreg((31 << 11) | 4);
+    }
 #endif
     static_assert(F <= 256, "one parameter triple per thread");
     const bool bn = out2 || ACT;                                         // s2 / t2 are in use
@@ -714,6 +733,7 @@ __global__ __launch_bounds__(256, (F == 128 ? 4 : 2)) void k_conv3x3_sg(const fl
     }
 #ifdef TG_CONV_STAMP
     TG_CSTAMP(6);                                                        // every store issued
+    if (drec) { drec[1] = __builtin_readcyclecounter(); drec[3] = __builtin_amdgcn_s_memrealtime(); }
     TG_VMCNT(0);
     TG_CSTAMP(7);                                                        // and written: the wave can end
 #endif
@@ -2208,8 +2228,8 @@ int forward_t(tg_ctx* ctx, Net* n, const float* obs, int rows, float* policy, fl
                 return;
             }
             if (chain == CHAIN_DMA) {
-                // one workgroup per (range of 128 boards, position), the count rounded up to the XCD-contiguous order's multiple of 8
-                const int grid_sd = ((rows + 127) / 128 * P + 7) / 8 * 8;
+                // one workgroup per (range of 128 boards, position): 8 x the longest XCD list of the launch order (conv_rows.h)
+                const int grid_sd = conv_launch_grid((rows + 127) / 128, S);
                 // conv1 activates the stream on load (sin), or reads the copy that an attention layer left activated in bufAct; conv2
                 // (EPI 1) never reads s2 / t2
                 auto* k1 = sin ? &k_conv3x3_sg<S, F, 0, true> : &k_conv3x3_sg<S, F, 0>;
@@ -2776,6 +2796,12 @@ int tg_net_load_poll(tg_ctx* ctx, int wait, int* pending) {
 int tg_debug_conv_stamps(unsigned long long* out, int n) {
     if (n > 96) n = 96;
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_conv_stamp), sizeof(unsigned long long) * n) == hipSuccess ? 0 : -1;
+}
+// the drain records of one conv (epi 0 / 1): `n` workgroups x 6 words
+int tg_debug_conv_drain(unsigned long long* out, int epi, int n) {
+    if (n > TG_DRAIN_CAP) n = TG_DRAIN_CAP;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_conv_drain), sizeof(unsigned long long) * TG_DRAIN_REC * n,
+                               sizeof(unsigned long long) * TG_DRAIN_REC * TG_DRAIN_CAP * (epi ? 1 : 0)) == hipSuccess ? 0 : -1;
 }
 #endif
 #ifdef TG_ATT_STAMP
