@@ -269,6 +269,34 @@ int tg_sp_final(tg_ctx* ctx, float* score /*[G]*/, float* terr /*[G][S*S]*/, int
 int tg_sp_stats(tg_ctx* ctx, uint64_t* sims, uint64_t* evals, uint64_t* depth_sum, uint64_t* tie_draws, int32_t* errors,
                 int32_t* max_slots);
 
+/* ---- evaluation cache: positions already evaluated skip the network ---------------------------------------------------------------
+ * Opt-in, per context, exact.  The network's output for a row of the evaluation batch is a pure function of the row's bit-packed
+ * planes, the live weight set and the symmetry mode, and the forward computes identical bits for identical rows wherever they stand
+ * in a batch; so a table keyed by the full bits (a hash only picks the bucket, every word is compared before a hit) changes no
+ * visit count, move or float in the tree -- it only takes rows out of the forward.  With a cache configured tg_sp_eval and
+ * tg_sp_search probe the table, fold the rows of one batch that hold the same position into one, run the forward on the rest (one
+ * 4-byte read-back per batch gives the host their number), and insert what was evaluated.  tg_sp_set_eval (a host evaluator is not
+ * known to be pure) and tg_net_predict never touch it.
+ *
+ * tg_sp_eval_cache: entries == 0 frees the cache (the context is the uncached engine again: nothing else is launched or
+ * allocated); otherwise a 4-way set-associative table of `entries` rounded up to whole buckets plus staging for one batch,
+ * 16 + 4 * obs_words + 4 * (A + 1) bytes per entry (452 B at 9x9, 1920 B at 19x19 with 10 planes).  An existing cache is replaced
+ * (contents and counters start again).  TG_ERR_STATE while an evaluation batch is pending, TG_ERR_HIP (the message names the
+ * bytes asked for) when the allocation fails, TG_ERR_ARG for a context without games or more than 2^31 entries.
+ * Invalidation is a generation number, nothing is swept: every change of the evaluator -- tg_net_load / tg_net_load_arch, an
+ * asynchronous refresh at the moment it is adopted, tg_net_set_symmetry with another mode or argument -- and
+ * tg_sp_eval_cache_clear make every entry written so far a miss.  Snapshots do not hold the cache and tg_sp_restore leaves it
+ * alone (entries are keyed by position and generation, not by game).
+ * tg_sp_eval_cache_stats: cumulative since the cache was created; lookups = hits + batch_duplicates + evaluated, rows requested /
+ * served from the table / served by another row of the same batch / sent through the network; inserts, and dropped_inserts = an
+ * evaluated row that lost the claim on its way of the table to another row of the same batch (harmless: it is evaluated again next
+ * time).  Which of two keys wins a contested way may differ from run to run, so may the counters; results never do.  Any pointer
+ * may be NULL; without a cache everything is 0.  tg_sp_stats keeps counting the rows requested as evals. */
+int tg_sp_eval_cache(tg_ctx* ctx, uint64_t entries);
+int tg_sp_eval_cache_clear(tg_ctx* ctx);
+int tg_sp_eval_cache_stats(tg_ctx* ctx, uint64_t* lookups, uint64_t* hits, uint64_t* batch_duplicates, uint64_t* evaluated,
+                           uint64_t* inserts, uint64_t* dropped_inserts, uint64_t* entries, uint64_t* bytes);
+
 /* ---- checkpoint and resume: the whole engine as one flat byte buffer ------------------------------------------------------------
  * The reference checkpoints its replay buffer (replay_buffer.py:49-87, transgo.py:225-250); its games in flight are lost with the
  * process.  Here the population itself can be put down and picked up again, or forked (one snapshot restored into two contexts).
@@ -379,6 +407,11 @@ int tg_prof_skipped(tg_ctx* ctx, int64_t* launches);
  * scored by PUCT summed over all selection levels since the last reset (mean fan-out = children_scored / depth_sum). */
 int tg_prof_enable_tree(tg_ctx* ctx, int on, int max_waves);
 int tg_prof_read_tree(tg_ctx* ctx, double* collect_ms, double* absorb_ms, int64_t* waves, uint64_t* children_scored);
+/* The same for a context with an evaluation cache (TG_ERR_STATE without one), per cached batch: probe_ms = probe, in-batch
+ * duplicates and the dense list; readback_ms = the stream's idle gap while the host reads the number of rows left; net_ms = the
+ * forward on those rows; insert_ms = scatter and insert.  Batches that found the event pool full are not in the totals. */
+int tg_prof_enable_eval_cache(tg_ctx* ctx, int on, int max_batches);
+int tg_prof_read_eval_cache(tg_ctx* ctx, double* probe_ms, double* readback_ms, double* net_ms, double* insert_ms, int64_t* batches);
 
 /* ---- device-resident replay store + batch sampler (replaces replay_buffer.py:30-47 + the stacking of trainer.py:46-54) ----
  * Positions are stored once, un-augmented and compact; entry e of the reference's ring of augmented tuples is

@@ -8,7 +8,7 @@ name=$1; src=$2; shift 2
 mkdir -p ../../build
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -Wall -Wno-unused-function "$@" -c $src -o ../../build/${src%.hip}_$name.o
 objs=""
-for o in env.o engine.o net.o replay.o snapshot.o rollout.o symmetry.o rng_host.o compat.o; do
+for o in env.o engine.o net.o replay.o snapshot.o rollout.o symmetry.o eval_cache.o rng_host.o compat.o; do
   if [ $o = ${src%.hip}.o ]; then objs="$objs ../../build/${src%.hip}_$name.o"; else objs="$objs $o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../build/libtransgo_hip_$name.so $objs

@@ -70,6 +70,11 @@ SIGNATURES = {
     "tg_sp_finished": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "tg_sp_harvest": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "tg_sp_stats": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint64)] * 4 + [ctypes.POINTER(ctypes.c_int32)] * 2),
+    "tg_sp_eval_cache": (ctypes.c_int, [_vp, ctypes.c_uint64]),
+    "tg_sp_eval_cache_clear": (ctypes.c_int, [_vp]),
+    "tg_sp_eval_cache_stats": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint64)] * 8),
+    "tg_prof_enable_eval_cache": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
+    "tg_prof_read_eval_cache": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(ctypes.c_int64)]),
     "tg_net_blob_floats": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "tg_net_load": (ctypes.c_int, [_vp, _vp, ctypes.c_size_t, ctypes.c_int]),
     "tg_net_blob_floats_arch": (ctypes.c_size_t, [ctypes.c_int] * 3 + [ctypes.c_char_p]),

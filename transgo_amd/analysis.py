@@ -19,7 +19,7 @@ def vertex(action, board_size):
     return f"{_COLUMNS[action % S]}{S - action // S}"
 
 
-def analyse(engine, states, num_simulation=0, depth=16, symmetry=None):
+def analyse(engine, states, num_simulation=0, depth=16, symmetry=None, eval_cache_entries=None):
     """Search every position of `states` ([N, state_size] uint8 blobs of transgo_amd.environment.GoEnv) in evaluation mode -- a
     fresh root, no root noise, as select_action's prologue (self_play.py:689-700) -- and read the trees out.  The engine's games
     are re-rooted (`reset_from`), so whatever they held is gone; the engine must have been `reset` once before (that seeds the
@@ -33,10 +33,15 @@ def analyse(engine, states, num_simulation=0, depth=16, symmetry=None):
       pv      list of actions, most-visited child at each level (ties: lowest action), at most `depth`; pv_visits their visits
     symmetry: "none" | "position" | "mean8" | an int s (transgo_amd.symmetry) evaluates under that mode for this call only; the
     engine's own mode is put back afterwards, also when the search raises.  None = the engine's own.
+    eval_cache_entries: an int gives the engine an exact evaluation cache of that many entries first (SelfPlayEngine.set_eval_cache;
+    0 frees it) and leaves it in place for later calls -- the same results, fewer network rows when positions repeat within or
+    across the searched trees.  None = the engine as it is.
     """
     states = np.ascontiguousarray(states, np.uint8)
     if states.ndim != 2:
         raise ValueError("states must be [N, state_size]")
+    if eval_cache_entries is not None:
+        engine.set_eval_cache(eval_cache_entries)
     if symmetry is not None:
         old = engine.get_symmetry()
         engine.set_symmetry(symmetry, old[1] if symmetry == "position" and old[0] == 2 else 0)

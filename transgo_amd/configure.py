@@ -33,6 +33,8 @@ class Config:
         self.eval_symmetry = "none"              # "position": every evaluation in one orientation chosen from (symmetry_seed, position);
                                                  # "mean8": the mean over all eight (match play, analysis); transgo_amd/symmetry.py.
         self.symmetry_seed = 0                   # Only "none" keeps bit parity with the reference's self-play
+        self.eval_cache_entries = 0              # > 0: exact evaluation cache of that many positions per engine (452 B each at 9x9, 1920 B
+                                                 # at 19x19): rows already evaluated skip the network, results stay bit-identical
         self.batch_size = 2048
         self.train_play_ratio = 7500 / 100000    # configure.py:61
         self.adjust_train_play_ratio = True

@@ -44,6 +44,7 @@ struct EngineDev {
 };
 
 struct Net;                          // net.hip
+struct EvalCache;                    // eval_cache.hip
 
 struct Engine {
     int G = 0, R = 0, rows_cap = 0;
@@ -71,14 +72,22 @@ struct Engine {
     std::vector<double> h_noise;
     std::vector<int32_t> h_nchild;
     Net* net = nullptr;
+    EvalCache* cache = nullptr;      // tg_sp_eval_cache: nullptr = every pending row goes through the network (nothing else is launched)
     // HIP-event timing of the tree stage (k_collect, k_absorb) on the engine's stream, switched by tg_prof_enable
     bool tprof = false; std::vector<hipEvent_t> tev; size_t tev_used = 0; double collect_ms = 0, absorb_ms = 0; long tree_waves = 0;
     std::vector<char> tev_kind;
 };
 
+// eval_cache.hip -- the exact evaluation cache around tg_net_forward
+int eval_cache_run(tg_ctx* ctx, int rows);      // the pending batch: probe, in-batch duplicates, forward on the rest, scatter + insert
+void eval_cache_invalidate(tg_ctx* ctx);        // the evaluator changed (weights, precision, symmetry): no entry made so far may hit again
+void eval_cache_destroy(tg_ctx* ctx);
+
 }  // namespace tg
 
 extern "C" int tg_net_forward(tg_ctx* ctx, int rows);   // pending batch (obs_bits through row_slot) -> policy[rows], value[rows] on ctx->stream
+// the same for `rows` rows listed in `slot` (entries of obs_bits), outputs row-indexed into the caller's buffers of >= rows rows
+extern "C" int tg_net_forward_rows(tg_ctx* ctx, int rows, const int32_t* slot, float* policy, float* value);
 extern "C" void tg_net_destroy(tg_ctx* ctx);
 extern "C" int tg_net_adopt_ready(tg_ctx* ctx);         // tg_sp_begin_move: a completed background weight refresh becomes the live set
 extern "C" int tg_net_load_arch(tg_ctx* ctx, const char* arch, const float* blob, size_t n_floats, int rows_cap);

@@ -1166,6 +1166,7 @@ void tg_engine_destroy(tg_ctx* ctx) {
     if (e->h_rng) (void)hipHostFree(e->h_rng);
     e->obs_f32.release(); e->readout.release(); e->snap_tab.release(); e->snap_stage.release(); e->hv_obs.release(); e->hv_cnt.release(); e->hv_z.release(); e->hv_own.release(); e->hv_pl.release(); e->hv_game.release();
     for (hipEvent_t ev : e->tev) (void)hipEventDestroy(ev);
+    eval_cache_destroy(ctx);
     tg_net_destroy(ctx);
     delete e;
     ctx->eng = nullptr;
@@ -1299,7 +1300,7 @@ int tg_sp_eval(tg_ctx* ctx) {
     int32_t cnt[CNT_N];
     int rc = read_counters(ctx, cnt);
     if (rc) return rc;
-    rc = tg_net_forward(ctx, cnt[CNT_ROWS]);
+    rc = e->cache ? eval_cache_run(ctx, cnt[CNT_ROWS]) : tg_net_forward(ctx, cnt[CNT_ROWS]);
     if (rc) return rc;
     e->batch_ready = true;
     return TG_OK;
@@ -1390,7 +1391,7 @@ int tg_sp_search(tg_ctx* ctx, int32_t* n_waves) {
         if (rc) return rc;
         if (rows > 0) {
             if (g_trace_launch) { fprintf(stderr, "[tg %ld] network forward, %d rows\n", ++g_trace_seq, rows); fflush(stderr); }
-            rc = tg_net_forward(ctx, rows); if (rc) return rc; ctx->eng->batch_ready = true;
+            rc = ctx->eng->cache ? eval_cache_run(ctx, rows) : tg_net_forward(ctx, rows); if (rc) return rc; ctx->eng->batch_ready = true;
             if (g_trace_launch) TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
         }
         rc = tg_sp_absorb(ctx);

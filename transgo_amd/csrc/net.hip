@@ -2579,6 +2579,7 @@ int adopt_pending(tg_ctx* ctx, Net* n, bool wait) {
     n->active ^= 1;
     bind_weights(n, n->active);
     n->pending = false;
+    tg::eval_cache_invalidate(ctx);                                     // another weight set: cached outputs are the old one's
     TG_HIP(ctx, hipEventRecord(n->swapped, ctx->stream));               // kernels already queued may still read the retired set
     return TG_OK;
 }
@@ -2739,6 +2740,7 @@ int tg_net_load_arch(tg_ctx* ctx, const char* arch_c, const float* blob, size_t 
     TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     n->active = k;
     bind_weights(n, k);
+    tg::eval_cache_invalidate(ctx);
     return TG_OK;
 }
 
@@ -2836,9 +2838,15 @@ int tg_net_adopt_ready(tg_ctx* ctx) {
 int tg_net_forward(tg_ctx* ctx, int rows) {
     Engine* e = ctx->eng;
     if (!e || !e->net) TG_FAIL(ctx, TG_ERR_STATE, "no network weights loaded (tg_net_load)");
+    return tg_net_forward_rows(ctx, rows, e->dev.row_slot, e->dev.policy, e->dev.value);
+}
+
+int tg_net_forward_rows(tg_ctx* ctx, int rows, const int32_t* slot, float* policy, float* value) {
+    Engine* e = ctx->eng;
+    if (!e || !e->net) TG_FAIL(ctx, TG_ERR_STATE, "no network weights loaded (tg_net_load)");
     Net* n = e->net;
-    n->in_bits = e->dev.obs_bits; n->in_slot = e->dev.row_slot; n->in_words = e->dev.obs_words;
-    const int rc = forward_sym(ctx, n, nullptr, rows, e->dev.policy, e->dev.value, nullptr);
+    n->in_bits = e->dev.obs_bits; n->in_slot = slot; n->in_words = e->dev.obs_words;
+    const int rc = forward_sym(ctx, n, nullptr, rows, policy, value, nullptr);
     n->in_bits = nullptr; n->in_slot = nullptr;
     return rc;
 }

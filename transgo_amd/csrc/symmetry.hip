@@ -191,8 +191,10 @@ int tg_net_set_symmetry(tg_ctx* ctx, int mode, uint32_t arg) {
         TG_FAIL(ctx, TG_ERR_ARG, "tg_net_set_symmetry: a fixed symmetry is 0..7, got " + std::to_string(arg));
     if (ctx->eng && ctx->eng->batch_kind != tg::BATCH_NONE)
         TG_FAIL(ctx, TG_ERR_STATE, "tg_net_set_symmetry: the evaluator changes at a move boundary only (an evaluation batch is pending)");
+    const uint32_t new_arg = (mode == tg::SYM_FIXED || mode == tg::SYM_POSITION) ? arg : 0u;
+    if (mode != ctx->sym.mode || new_arg != ctx->sym.arg) tg::eval_cache_invalidate(ctx);
     ctx->sym.mode = mode;
-    ctx->sym.arg = (mode == tg::SYM_FIXED || mode == tg::SYM_POSITION) ? arg : 0u;
+    ctx->sym.arg = new_arg;
     return TG_OK;
 }
 

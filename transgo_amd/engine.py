@@ -98,11 +98,22 @@ def choose_moves_batch(visits, steps, u, live, selfplay=True):
     return actions, pis
 
 
+def eval_cache_stats(engine):
+    """The evaluation-cache counters of a SelfPlayEngine (or of anything that holds one as `.engine`) as a dict."""
+    eng = getattr(engine, "engine", engine)
+    ctx = getattr(eng, "ctx", None)
+    if ctx is None or not getattr(ctx, "h", None):
+        raise _lib.TransgoError("eval_cache_stats: no engine context (the engine was never created or is closed)")
+    v = [ctypes.c_uint64() for _ in SelfPlayEngine.EVAL_CACHE_STATS]
+    ctx.call("tg_sp_eval_cache_stats", *[ctypes.byref(x) for x in v])
+    return {k: int(x.value) for k, x in zip(SelfPlayEngine.EVAL_CACHE_STATS, v)}
+
+
 class SelfPlayEngine:
     def __init__(self, n_games, board_size=9, num_simulation=210, parallel_readouts=4, c_puct1=3, c_puct2=0.05,
                  wu_loss=2, komi=7.5, max_step=120, encode_dim=10, net_blocks=6, net_filters=128, arena_slots=0,
                  device=0, evaluator=None, net_precision="f32", record_games=True, pool_slots=0, eval_symmetry="none",
-                 symmetry_seed=0):
+                 symmetry_seed=0, eval_cache_entries=0):
         cfg = _lib.default_config()
         cfg.record_games = 1 if record_games else 0       # per-move records in HBM for tg_sp_harvest (self-play); evaluation matches need none
         cfg.net_precision = {"f32": 0, "f16": 1, "f16r": 2, "f32x3": 3}[net_precision]
@@ -123,6 +134,8 @@ class SelfPlayEngine:
         self._host_symmetry = (0, 0)
         if _symmetry.parse_mode(eval_symmetry, symmetry_seed)[0] != 0:
             self.set_symmetry(eval_symmetry, symmetry_seed)
+        if eval_cache_entries:
+            self.set_eval_cache(eval_cache_entries)
 
     def close(self):
         self.ctx.close()
@@ -145,6 +158,24 @@ class SelfPlayEngine:
         m, a = ctypes.c_int(), ctypes.c_uint32()
         self.ctx.call("tg_net_get_symmetry", ctypes.byref(m), ctypes.byref(a))
         return int(m.value), int(a.value)
+
+    # ---- evaluation cache (tg_sp_eval_cache) ------------------------------------------------------------------
+    EVAL_CACHE_STATS = ("lookups", "hits", "batch_duplicates", "evaluated", "inserts", "dropped_inserts", "entries", "bytes")
+
+    def set_eval_cache(self, entries):
+        """An exact cache of network outputs keyed by the full bit-packed position: rows already evaluated under the live weights
+        and symmetry mode, and rows that repeat inside one batch, skip the forward; results are bit-identical to the uncached
+        engine.  `entries` is rounded up to whole 4-way buckets (452 B per entry at 9x9, 1920 B at 19x19); 0 frees the cache.
+        Legal at a move boundary only.  A host `evaluator` is never cached (it is not known to be pure)."""
+        self.ctx.call("tg_sp_eval_cache", int(entries))
+
+    def clear_eval_cache(self):
+        """Every entry written so far becomes a miss (a generation bump; weight loads and symmetry changes do it themselves)."""
+        self.ctx.call("tg_sp_eval_cache_clear")
+
+    def eval_cache_stats(self):
+        """tg_sp_eval_cache_stats as a dict (EVAL_CACHE_STATS): cumulative since the cache was created, all 0 without one."""
+        return eval_cache_stats(self)
 
     # ---- evaluation of the pending batch --------------------------------------------------------------------------------
     def _evaluate(self, rows=None):

@@ -78,7 +78,8 @@ class BatchedSelfPlay:
     lists (observations, visit counts, players; self_play.py:917-926) lives in HBM inside the engine; a finished game leaves
     it as a `records.Harvest` batch -- in device memory when the consumer is on the GPU too."""
 
-    def __init__(self, config, n_games, device=0, rank=0, world=1, evaluator=None, arena_slots=0, seed_fn=None, pool_slots=0):
+    def __init__(self, config, n_games, device=0, rank=0, world=1, evaluator=None, arena_slots=0, seed_fn=None, pool_slots=0,
+                 eval_cache_entries=None):
         self.config, self.G, self.rank, self.world = config, n_games, rank, world
         self.S = config.board_size
         self.filters = getattr(config, "num_features", 128)
@@ -94,7 +95,8 @@ class BatchedSelfPlay:
             arena_slots=arena_slots, device=device, evaluator=evaluator,
             pool_slots=pool_slots or getattr(config, "tree_pool_slots", 0),
             net_precision=getattr(config, "inference_dtype", "f32"),
-            eval_symmetry=getattr(config, "eval_symmetry", "none"), symmetry_seed=getattr(config, "symmetry_seed", 0))
+            eval_symmetry=getattr(config, "eval_symmetry", "none"), symmetry_seed=getattr(config, "symmetry_seed", 0),
+            eval_cache_entries=getattr(config, "eval_cache_entries", 0) if eval_cache_entries is None else eval_cache_entries)
         self.seed_fn = seed_fn
         self.games_started = np.zeros(n_games, np.int64)
         self.seeds = np.zeros(n_games, np.uint32)          # seed of the game now running in each slot
