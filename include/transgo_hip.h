@@ -165,6 +165,14 @@ int tg_sp_expand_roots(tg_ctx* ctx);                                       /* ro
 /* get_action_probs prologue (self_play.py:659-663): Dirichlet(0.03) root noise when selfplay != 0, and the visit
  * target N0 + num_simulation (<= 0: cfg.num_simulation). */
 int tg_sp_begin_move(tg_ctx* ctx, int selfplay, int num_simulation);
+/* The same prologue with a per-game noise switch, visit budget and record switch (playout cap randomization):
+ * noise u8[G] (NULL = no game is noised): Dirichlet root noise for the games with noise[g] != 0 only -- the MT19937 stream of
+ * any other game is not advanced; num_simulation i32[G]: the game's target is N0 + num_simulation[g] (<= 0: cfg.num_simulation);
+ * record u8[G] (NULL = every game records): with record[g] == 0 the ply the next tg_sp_play plays is kept out of the training
+ * positions -- the game's record still holds it, marked, and tg_sp_finished / tg_sp_harvest skip it.  The switch lives until
+ * that tg_sp_play; tg_sp_reset, tg_sp_reset_from and tg_sp_restore put it back to "record".  tg_sp_begin_move(ctx, selfplay, n)
+ * is this call with noise = selfplay for every game, the same n and record = NULL. */
+int tg_sp_begin_move_games(tg_ctx* ctx, const uint8_t* noise, const int32_t* num_simulation, const uint8_t* record);
 
 /* Front half of WP_MCTS.run (self_play.py:616-646) for every active game.  n_active = games still below their
  * target before this wave; n_rows = leaves awaiting evaluation. */
@@ -248,7 +256,9 @@ int tg_sp_tree_truncations(tg_ctx* ctx, uint64_t* blocks);
 int tg_sp_pool_stats(tg_ctx* ctx, uint64_t* pool_slots, uint64_t* high_water_slots, uint64_t* in_use_slots, uint64_t* exhausted);
 
 /* ---- finished games -> training positions, on the device (self_play.py:929-967) ------------------------------------------
- * Games the LAST tg_sp_play finished, in ascending slot order, and the number of recorded positions (= moves) they hold. */
+ * Games the LAST tg_sp_play finished, in ascending slot order, and the number of recorded positions they hold (= their moves,
+ * unless tg_sp_begin_move_games kept plies out of the record: those are not counted, not harvested, and a game may contribute
+ * no position at all -- tg_sp_harvest then lists it with n_moves = 0). */
 int tg_sp_finished(tg_ctx* ctx, int32_t* n_games, int32_t* n_positions);
 /* Their positions as one position-major batch, game after game in that order, plies ascending -- the arrays
  * tg_replay_append(_dev) takes: obs_bits u32[n_positions][ceil(C*S*S/32)] (env.encode bit-packed, bit i = plane-major flat
@@ -446,6 +456,10 @@ uint32_t tg_host_mt_next32(tg_mt19937* s);
 double tg_host_mt_random_sample(tg_mt19937* s);                     /* random_sample(): the draw inside choice(A, p=) (self_play.py:683) */
 int32_t tg_host_mt_choice_index(tg_mt19937* s, int32_t k);          /* index drawn by choice(list of k) (self_play.py:709) */
 int tg_host_mt_dirichlet(tg_mt19937* s, double alpha, int32_t n, double* out);   /* dirichlet([alpha]*n) (self_play.py:93) */
+/* Playout cap randomization: the 24-bit draw that decides whether ply `ply` of the game seeded `seed` is searched in full --
+ * mix(mix(cap_seed << 32 | seed) ^ ply) >> 40 with mix = the splitmix64 finaliser; full when draw < floor(p_full * 2^24).  A
+ * pure function of its arguments: no game's MT19937 stream is touched (transgo_amd/playout_cap.py is the same in NumPy). */
+uint32_t tg_host_cap_draw(uint32_t seed, int32_t ply, uint32_t cap_seed);
 /* getSubEncode (go_env.h:70, board.cc:1166-1271) with the board size as an argument: crops channels x S x S 32-bit planes into
  * cut_num (<= 5) channels x s x s windows -- the four corners, then the centre.  Host arrays; no GPU needed. */
 void tg_host_sub_encode(int board_size, const void* encode, void* sub_encode, int sub_board_size, int channels, int cut_num);

@@ -52,6 +52,7 @@ SIGNATURES = {
     "tg_sp_eval": (ctypes.c_int, [_vp]),
     "tg_sp_expand_roots": (ctypes.c_int, [_vp]),
     "tg_sp_begin_move": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
+    "tg_sp_begin_move_games": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "tg_sp_collect": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "tg_sp_absorb": (ctypes.c_int, [_vp]),
     "tg_sp_search": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int32)]),
@@ -113,6 +114,7 @@ SIGNATURES = {
     "tg_host_mt_choice_index": (ctypes.c_int32, [ctypes.POINTER(TgMt19937), ctypes.c_int32]),
     "tg_host_sub_encode": (None, [ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "tg_host_mt_dirichlet": (ctypes.c_int, [ctypes.POINTER(TgMt19937), ctypes.c_double, ctypes.c_int32, _vp]),
+    "tg_host_cap_draw": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32]),
 }
 
 

@@ -35,6 +35,11 @@ class Config:
         self.symmetry_seed = 0                   # Only "none" keeps bit parity with the reference's self-play
         self.eval_cache_entries = 0              # > 0: exact evaluation cache of that many positions per engine (452 B each at 9x9, 1920 B
                                                  # at 19x19): rows already evaluated skip the network, results stay bit-identical
+        self.playout_cap_p_full = 1.0            # < 1: playout cap randomization (transgo_amd/playout_cap.py) -- every self-play move is a
+                                                 # full search (num_simulation, root noise, recorded) with this probability, else a fast one
+        self.playout_cap_fast = 0                # simulations of a fast search (no root noise, not a training position); needed when p_full < 1
+        self.playout_cap_seed = 0                # seed of the full / fast draws (a hash of game seed, ply and this; no game's RNG stream is used)
+        self.playout_cap_fast_noise = False      # True: fast searches get root noise too.  Only p_full = 1.0 keeps parity with the reference
         self.batch_size = 2048
         self.train_play_ratio = 7500 / 100000    # configure.py:61
         self.adjust_train_play_ratio = True
@@ -42,6 +47,8 @@ class Config:
         self.learn_rate = 6.5e-5
         for k, v in over.items():
             setattr(self, k, v)
+        from .playout_cap import check_config
+        check_config(self)
 
     def epsilon_by_frame(self, game_step):       # configure.py:75-79
         return 0.65 + (1.0 - 0.65) * math.exp(-1. * game_step / 10)

@@ -37,7 +37,9 @@ struct EngineDev {
     // per-game record of the moves played so far (the observation/pi/player lists of self_play.py:917-926), ply-major per game
     uint32_t* hist_obs = nullptr;   // [G][hist_T][obs_words]  env.encode(root) bit-packed (bit i = plane-major flat index i)
     int32_t* hist_cnt = nullptr;    // [G][hist_T][A]          raw root visit counts
-    uint8_t* hist_pl = nullptr;     // [G][hist_T]             side to move
+    uint8_t* hist_pl = nullptr;     // [G][hist_T]             side to move (1 / 2); bit 0x80 (kPlySkip): the ply is not a training position
+    uint8_t* ply_skip = nullptr;    // [G]  != 0: the ply the next k_play plays is kept out of the harvest (tg_sp_begin_move_games sets it,
+                                    //      k_play consumes it; every reset and restore clears it)
     int hist_T = 0, obs_words = 0, G = 0;
     SearchCfg sc;
     RulesCfg rules;
@@ -71,6 +73,8 @@ struct Engine {
     DevBuf snap_tab, snap_stage;     // snapshot.hip: scan offsets, and the packed snapshot on its way to / from a host buffer
     std::vector<double> h_noise;
     std::vector<int32_t> h_nchild;
+    std::vector<int32_t> h_sims, h_rec;       // tg_sp_begin_move_games: the per-game budgets; tg_sp_play: recorded plies of the games it finished
+    std::vector<uint8_t> h_flags;             // tg_sp_begin_move_games: noise switch [G] | skip switch [G]
     Net* net = nullptr;
     EvalCache* cache = nullptr;      // tg_sp_eval_cache: nullptr = every pending row goes through the network (nothing else is launched)
     // HIP-event timing of the tree stage (k_collect, k_absorb) on the engine's stream, switched by tg_prof_enable

@@ -270,12 +270,14 @@ __global__ __launch_bounds__(64) void k_expand_roots(EngineDev d) {
 }
 
 // Dirichlet root noise (self_play.py:90-95): prior <- prior*(1-0.25) + noise*0.25, float32*float -> float32, + float64
+// mask (nullptr = every game): only the games with mask[g] != 0 are noised (tg_sp_begin_move_games)
 template <int S>
-__global__ __launch_bounds__(64) void k_noise(EngineDev d, const double* noise) {
+__global__ __launch_bounds__(64) void k_noise(EngineDev d, const double* noise, const uint8_t* mask) {
     constexpr int HS = TreeGeo<S>::HS;
     const int g = blockIdx.x, lane = lane_id();
     GameCtl* c = &d.ctl[g];
     if (c->finished || c->error) return;
+    if (mask && !mask[g]) return;
     NodeRec* arena = d.arena;
     const int blk = arena[c->root].block;
     const int nchild = hdr_of<S>(arena, blk)->nchild;
@@ -289,10 +291,12 @@ __global__ __launch_bounds__(64) void k_noise(EngineDev d, const double* noise) 
 }
 
 template <int S>
-__global__ __launch_bounds__(64) void k_begin(EngineDev d, int sims) {
+__global__ __launch_bounds__(64) void k_begin(EngineDev d, int sims, const int32_t* sims_g, const uint8_t* skip) {
     const int g = blockIdx.x;
     if (lane_id() != 0) return;
     GameCtl* c = &d.ctl[g];
+    if (sims_g) sims = sims_g[g];                                     // per-game budget (tg_sp_begin_move_games)
+    d.ply_skip[g] = skip ? skip[g] : 0;                               // consumed by this move's k_play
     c->n_target = d.arena[c->root].n + sims;                          // self_play.py:662-663
     c->searching = (c->finished || c->error) ? 0 : 1;
     c->active = c->searching;
@@ -714,9 +718,11 @@ __global__ __launch_bounds__(64) void k_tree_pv(EngineDev d, int D, int32_t* o_a
 
 // update_with_action (self_play.py:857-872) + tree compaction into the other half arena.
 // Before the root moves on, the game's record gets this move's entry -- env.encode(root) bit-packed, the raw visit counts and
-// the side to move: what self_play.py:917-926 appends to its three Python lists.
+// the side to move: what self_play.py:917-926 appends to its three Python lists.  A ply whose search was told not to record
+// (ply_skip, tg_sp_begin_move_games) is written all the same, with kPlySkip set in its side-to-move byte; for a game this move
+// finishes, rec_out = the number of its plies without the mark (the positions k_harvest will write).
 template <int S>
-__global__ __launch_bounds__(64) void k_play(EngineDev d, const int32_t* actions, uint8_t* done_out, int32_t* moves_out) {
+__global__ __launch_bounds__(64) void k_play(EngineDev d, const int32_t* actions, uint8_t* done_out, int32_t* moves_out, int32_t* rec_out) {
     using G = Geo<S>;
     constexpr int HS = TreeGeo<S>::HS, NPASS = TreeGeo<S>::NPASS;
     __shared__ WaveLds<S> lds;
@@ -725,7 +731,8 @@ __global__ __launch_bounds__(64) void k_play(EngineDev d, const int32_t* actions
     __shared__ int rsv_s[64];                          // chunk ids reserved for the new tree with one ticket draw
     const int g = blockIdx.x, lane = lane_id();
     GameCtl* c = &d.ctl[g];
-    if (lane == 0) d.game_nslot[g] = 0;
+    const uint8_t skip = d.ply_skip[g];
+    if (lane == 0) { d.game_nslot[g] = 0; rec_out[g] = 0; }
     if (c->finished || c->error) { if (lane == 0) { done_out[g] = c->error ? 2 : 1; moves_out[g] = c->moves; } return; }
     const SearchCfg& sc = d.sc;
     NodeRec* const pool = d.arena;
@@ -754,7 +761,7 @@ __global__ __launch_bounds__(64) void k_play(EngineDev d, const int32_t* actions
         bw.load_colors(st.bb[0], st.bb[1]);
         bw.analyze();
         encode_bits<S, 2>(bw, st, d.rules, bits_s, d.hist_obs + e * d.obs_words);
-        if (lane == 0) d.hist_pl[e] = st.next_player;
+        if (lane == 0) d.hist_pl[e] = skip ? (uint8_t)(st.next_player | kPlySkip) : (uint8_t)st.next_player;
     }
     bool ok;
     const bool done = state_step(bw, st, a, d.rules, /*check=*/false, &ok);      // self_play.py:859
@@ -863,13 +870,26 @@ __global__ __launch_bounds__(64) void k_play(EngineDev d, const int32_t* actions
         }
     }
     __syncthreads();
+    // the game is over: how many of its plies are training positions -- the earlier ones from their bytes (a ballot per 64 plies),
+    // this one from the switch it was just written with
+    int rec = 0;
+    if (done && d.hist_obs) {
+        const int nprev = t < d.hist_T ? t : d.hist_T;
+        const uint8_t* h_pl = d.hist_pl + (size_t)g * d.hist_T;
+        for (int i0 = 0; i0 < nprev; i0 += 64) {
+            const int i = i0 + lane;
+            rec += __popcll(ballot64(i < nprev && !(h_pl[i] & kPlySkip)));
+        }
+        if (t < d.hist_T && !skip) ++rec;
+    }
     // the old tree's chunks, and what was reserved and not needed, go back to the pool (poppable after k_pool_publish)
     pool_push(d, chunk_list(d, g, c->cur), c->n_chunks, na.rsv + na.rsv_i, na.rsv_n - na.rsv_i);
     if (lane == 0) {
         c->cur ^= 1; c->free_slot = na.free_slot; c->n_chunks = na.n_chunks; c->root = nroot;
         if (na.n_chunks * sc.chunk_slots > c->hw_slot) c->hw_slot = na.n_chunks * sc.chunk_slots;
         c->finished = done ? 1 : 0; c->searching = 0; c->active = 0; c->moves = t + 1;
-        done_out[g] = done ? 1 : 0; moves_out[g] = t + 1;
+        done_out[g] = done ? 1 : 0; moves_out[g] = t + 1; rec_out[g] = rec;
+        d.ply_skip[g] = 0;
     }
 }
 
@@ -877,7 +897,8 @@ __global__ __launch_bounds__(64) void k_play(EngineDev d, const int32_t* actions
 // sampler applies on the fly): one workgroup per finished game scores its final position (getScoreAndTerritory, getWinner)
 // and writes, for each of its recorded moves, the bit-packed observation, the raw visit counts, z = +1 if the mover is the
 // winner else -1 (:931-934) and the territory seen from the mover (:938-940), at the game's offset of a position-major batch
-// -- exactly the arrays tg_replay_append stores.
+// -- exactly the arrays tg_replay_append stores.  Plies marked kPlySkip (fast searches of playout cap randomization) are left
+// out: the game's positions are its unmarked plies, dense, in ply order; z and ownership come from the final position all the same.
 template <int S>
 __global__ __launch_bounds__(64) void k_harvest(EngineDev d, const int32_t* slot, const int32_t* off, uint32_t* o_obs,
                                                 int32_t* o_cnt, float* o_z, int8_t* o_own, uint8_t* o_pl, int32_t* o_winner,
@@ -885,6 +906,7 @@ __global__ __launch_bounds__(64) void k_harvest(EngineDev d, const int32_t* slot
     using G = Geo<S>;
     __shared__ WaveLds<S> lds;
     __shared__ int8_t terr_s[G::PPAD];
+    __shared__ int16_t src_s[kMaxPath];                                // ply of every harvested position (hist_T <= max_step <= kMaxPath - 2)
     const int f = blockIdx.x, lane = lane_id();
     const int g = slot[f];
     const size_t base = (size_t)off[f];
@@ -908,16 +930,33 @@ __global__ __launch_bounds__(64) void k_harvest(EngineDev d, const int32_t* slot
     const uint32_t* h_obs = d.hist_obs + (size_t)g * d.hist_T * d.obs_words;
     const int32_t* h_cnt = d.hist_cnt + (size_t)g * d.hist_T * G::A;
     const uint8_t* h_pl = d.hist_pl + (size_t)g * d.hist_T;
-    for (int i = lane; i < n * d.obs_words; i += 64) o_obs[base * d.obs_words + i] = h_obs[i];
-    for (int i = lane; i < n * G::A; i += 64) o_cnt[base * G::A + i] = h_cnt[i];
-    for (int i = lane; i < n; i += 64) {
-        const int pl = h_pl[i];
+    // the plies that are training positions (no kPlySkip mark), compacted in ply order: per 64 plies a ballot, and a popcount of the
+    // lanes below gives each kept ply its dense index; src_s[dense index] = ply
+    int m = 0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        const bool keep = i < n && !(h_pl[i] & kPlySkip);
+        const uint64_t b = ballot64(keep);
+        if (keep) src_s[m + __popcll(b & ((1ull << lane) - 1ull))] = (int16_t)i;
+        m += __popcll(b);
+    }
+    __syncthreads();
+    if (m == n) {                                                      // nothing was kept out: the record is the batch, word for word
+        for (int i = lane; i < n * d.obs_words; i += 64) o_obs[base * d.obs_words + i] = h_obs[i];
+        for (int i = lane; i < n * G::A; i += 64) o_cnt[base * G::A + i] = h_cnt[i];
+    } else {
+        const int W = d.obs_words;
+        for (int i = lane; i < m * W; i += 64) { const int tt = i / W, w = i - tt * W; o_obs[base * W + i] = h_obs[(size_t)src_s[tt] * W + w]; }
+        for (int i = lane; i < m * G::A; i += 64) { const int tt = i / G::A, a = i - tt * G::A; o_cnt[base * G::A + i] = h_cnt[(size_t)src_s[tt] * G::A + a]; }
+    }
+    for (int i = lane; i < m; i += 64) {
+        const int pl = h_pl[src_s[i]] & ~kPlySkip;
         o_z[base + i] = pl == winner ? 1.f : -1.f;
         if (o_pl) o_pl[base + i] = (uint8_t)pl;
     }
-    for (int i = lane; i < n * G::P; i += 64) {
+    for (int i = lane; i < m * G::P; i += 64) {
         const int tt = i / G::P, p = i - tt * G::P;
-        o_own[base * G::P + i] = h_pl[tt] == kBlack ? terr_s[p] : (int8_t)-terr_s[p];
+        o_own[base * G::P + i] = (h_pl[src_s[tt]] & ~kPlySkip) == kBlack ? terr_s[p] : (int8_t)-terr_s[p];
     }
 }
 
@@ -1043,6 +1082,55 @@ template <class F> void parallel_games(int n, F f) {
     for (auto& x : th) x.join();
 }
 
+// The get_action_probs prologue (self_play.py:659-663) behind both entry points.  noise_g == nullptr: every game is noised when
+// noise_all, none otherwise; sims_g == nullptr: every game's budget is `sims`; record_g == nullptr: every game records its ply.
+int begin_move(tg_ctx* ctx, const char* who, bool noise_all, const uint8_t* noise_g, int sims, const int32_t* sims_g, const uint8_t* record_g) {
+    Engine* e = ctx->eng;
+    const int G = e->G, A = ctx->A;
+    if (e->batch_kind != BATCH_NONE) TG_FAIL(ctx, TG_ERR_STATE, std::string(who) + ": an evaluation batch is pending");
+    // weights change between moves only (the reference swaps them at game start, self_play.py:913; with G games in lock step the
+    // move boundary is the closest point every game shares): one search = one weight set
+    { int rc = tg_net_adopt_ready(ctx); if (rc) return rc; }
+    // per-game switches: noise u8[G] at d_u8 + G, skip u8[G] at d_u8 + 2G (the first G bytes are tg_sp_play's / tg_sp_reset's);
+    // budgets i32[G] at d_i32 + G (behind k_root_info's child counts)
+    const uint8_t* d_noise_g = nullptr; const uint8_t* d_skip = nullptr; const int32_t* d_sims = nullptr;
+    if (noise_g || record_g) {
+        e->h_flags.assign((size_t)2 * G, 0);
+        bool any = false;
+        for (int g = 0; g < G; ++g) {
+            if (noise_g && noise_g[g]) { e->h_flags[g] = 1; any = true; }
+            if (record_g && !record_g[g]) e->h_flags[(size_t)G + g] = 1;
+        }
+        TG_HIP(ctx, hipMemcpyAsync(e->d_u8 + G, e->h_flags.data(), (size_t)2 * G, hipMemcpyHostToDevice, ctx->stream));
+        if (noise_g) { d_noise_g = e->d_u8 + G; noise_all = any; }
+        if (record_g) d_skip = e->d_u8 + 2 * (size_t)G;
+    }
+    if (sims_g) {
+        e->h_sims.resize(G);
+        for (int g = 0; g < G; ++g) e->h_sims[g] = sims_g[g] > 0 ? sims_g[g] : ctx->cfg.num_simulation;
+        TG_HIP(ctx, hipMemcpyAsync(e->d_i32 + G, e->h_sims.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, ctx->stream));
+        d_sims = e->d_i32 + G;
+    }
+    if (noise_all) {                                                   // root.dirichlet_prior(), self_play.py:659-660
+        int32_t* d_nchild = e->d_i32;
+        TG_LAUNCH(ctx, k_root_info, G, e->dev, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr,
+                  d_nchild, (float*)nullptr);
+        TG_HIP(ctx, hipMemcpyAsync(e->h_nchild.data(), d_nchild, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
+        TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        { int rc = rng_to_host(ctx); if (rc) return rc; }
+        // a game that is not noised draws nothing: its stream stays where it is
+        parallel_games(G, [&](int g) {
+            if (e->h_nchild[g] > 0 && (!noise_g || noise_g[g])) tg_host_mt_dirichlet(&e->h_rng[g], 0.03, e->h_nchild[g], &e->h_noise[(size_t)g * A]);
+        });
+        TG_HIP(ctx, hipMemcpyAsync(e->d_noise, e->h_noise.data(), sizeof(double) * (size_t)G * A, hipMemcpyHostToDevice, ctx->stream));
+        TG_LAUNCH(ctx, k_noise, G, e->dev, (const double*)e->d_noise, d_noise_g);
+    }
+    { int rc = rng_to_device(ctx); if (rc) return rc; }
+    TG_LAUNCH(ctx, k_begin, G, e->dev, sims, d_sims, d_skip);
+    TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return TG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1133,6 +1221,8 @@ int tg_engine_create(tg_ctx* ctx) {
         TG_HIP(ctx, hipMalloc((void**)&e->dev.hist_cnt, sizeof(int32_t) * n * A));
         TG_HIP(ctx, hipMalloc((void**)&e->dev.hist_pl, n));
     }
+    TG_HIP(ctx, hipMalloc((void**)&e->dev.ply_skip, (size_t)G));
+    TG_HIP(ctx, hipMemsetAsync(e->dev.ply_skip, 0, (size_t)G, ctx->stream));
     e->h_noise.resize((size_t)G * A);
     e->h_nchild.resize(G);
     e->arena_bytes = arena_bytes;
@@ -1161,7 +1251,7 @@ void tg_engine_destroy(tg_ctx* ctx) {
     if (!e) return;
     void* ptrs[] = {e->dev.arena, e->dev.ring, e->dev.pool, e->dev.chunk_ids, e->dev.ctl, e->dev.rng, e->dev.path_nodes, e->dev.path_len, e->dev.path_row, e->dev.row_slot,
                     e->dev.obs_bits, e->dev.game_nslot, e->dev.game_off, e->dev.game_act, e->dev.policy, e->dev.value, e->dev.counters, e->d_noise, e->d_i32, e->d_f32, e->d_u8,
-                    e->d_fin, e->dev.hist_obs, e->dev.hist_cnt, e->dev.hist_pl};
+                    e->d_fin, e->dev.hist_obs, e->dev.hist_cnt, e->dev.hist_pl, e->dev.ply_skip};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->h_rng) (void)hipHostFree(e->h_rng);
     e->obs_f32.release(); e->readout.release(); e->snap_tab.release(); e->snap_stage.release(); e->hv_obs.release(); e->hv_cnt.release(); e->hv_z.release(); e->hv_own.release(); e->hv_pl.release(); e->hv_game.release();
@@ -1187,6 +1277,7 @@ int tg_sp_reset(tg_ctx* ctx, const uint32_t* seeds, const uint8_t* mask) {
     parallel_games(G, [&](int g) { if (!mask || mask[g]) tg_host_mt_seed(&e->h_rng[g], seeds[g]); });
     for (int g = 0; g < G; ++g) if (!mask || mask[g]) e->h_moves[g] = 0;
     e->fin_slot.clear(); e->fin_off.clear(); e->fin_positions = 0;   // unharvested records of restarted slots are gone
+    TG_HIP(ctx, hipMemsetAsync(e->dev.ply_skip, 0, (size_t)G, ctx->stream));      // a move boundary: every game records again
     uint8_t* d_mask = nullptr;
     if (mask) {
         TG_HIP(ctx, hipMemcpyAsync(e->d_u8, mask, G, hipMemcpyHostToDevice, ctx->stream));
@@ -1226,6 +1317,7 @@ int tg_sp_reset_from(tg_ctx* ctx, const void* states, const uint8_t* mask) {
     if (mask) { TG_HIP(ctx, hipMemcpyAsync(e->d_u8, mask, G, hipMemcpyHostToDevice, ctx->stream)); d_mask = e->d_u8; }
     for (int g = 0; g < G; ++g) if (!mask || mask[g]) e->h_moves[g] = 0;
     e->fin_slot.clear(); e->fin_off.clear(); e->fin_positions = 0;
+    TG_HIP(ctx, hipMemsetAsync(e->dev.ply_skip, 0, (size_t)G, ctx->stream));
     // (unmasked slots are parked by k_reset and keep the one chunk they own until their next reset)
     hipLaunchKernelGGL(k_release, dim3(G), dim3(64), 0, ctx->stream, e->dev, (const uint8_t*)d_mask);
     hipLaunchKernelGGL(k_pool_publish, dim3(1), dim3(1), 0, ctx->stream, e->dev);
@@ -1318,30 +1410,14 @@ int tg_sp_expand_roots(tg_ctx* ctx) {
 
 int tg_sp_begin_move(tg_ctx* ctx, int selfplay, int num_simulation) {
     NEED_ENGINE(ctx);
-    Engine* e = ctx->eng;
-    const int G = e->G, A = ctx->A;
-    if (e->batch_kind != BATCH_NONE) TG_FAIL(ctx, TG_ERR_STATE, "tg_sp_begin_move: an evaluation batch is pending");
     if (num_simulation <= 0) num_simulation = ctx->cfg.num_simulation;
-    // weights change between moves only (the reference swaps them at game start, self_play.py:913; with G games in lock step the
-    // move boundary is the closest point every game shares): one search = one weight set
-    { int rc = tg_net_adopt_ready(ctx); if (rc) return rc; }
-    if (selfplay) {                                                    // root.dirichlet_prior(), self_play.py:659-660
-        int32_t* d_nchild = e->d_i32;
-        TG_LAUNCH(ctx, k_root_info, G, e->dev, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr,
-                  d_nchild, (float*)nullptr);
-        TG_HIP(ctx, hipMemcpyAsync(e->h_nchild.data(), d_nchild, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
-        TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        { int rc = rng_to_host(ctx); if (rc) return rc; }
-        parallel_games(G, [&](int g) {
-            if (e->h_nchild[g] > 0) tg_host_mt_dirichlet(&e->h_rng[g], 0.03, e->h_nchild[g], &e->h_noise[(size_t)g * A]);
-        });
-        TG_HIP(ctx, hipMemcpyAsync(e->d_noise, e->h_noise.data(), sizeof(double) * (size_t)G * A, hipMemcpyHostToDevice, ctx->stream));
-        TG_LAUNCH(ctx, k_noise, G, e->dev, (const double*)e->d_noise);
-    }
-    { int rc = rng_to_device(ctx); if (rc) return rc; }
-    TG_LAUNCH(ctx, k_begin, G, e->dev, num_simulation);
-    TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return TG_OK;
+    return begin_move(ctx, "tg_sp_begin_move", selfplay != 0, nullptr, num_simulation, nullptr, nullptr);
+}
+
+int tg_sp_begin_move_games(tg_ctx* ctx, const uint8_t* noise, const int32_t* num_simulation, const uint8_t* record) {
+    NEED_ENGINE(ctx);
+    if (!num_simulation) TG_FAIL(ctx, TG_ERR_ARG, "tg_sp_begin_move_games: num_simulation is NULL (one budget per game; <= 0 means cfg.num_simulation)");
+    return begin_move(ctx, "tg_sp_begin_move_games", false, noise, ctx->cfg.num_simulation, num_simulation, record);
 }
 
 int tg_sp_collect(tg_ctx* ctx, int32_t* n_active, int32_t* n_rows) {
@@ -1527,24 +1603,28 @@ int tg_sp_play(tg_ctx* ctx, const int32_t* actions, uint8_t* done) {
     if (e->batch_kind != BATCH_NONE) TG_FAIL(ctx, TG_ERR_STATE, "tg_sp_play: an evaluation batch is pending");
     int32_t* d_act = e->d_i32;
     TG_HIP(ctx, hipMemcpyAsync(d_act, actions, sizeof(int32_t) * G, hipMemcpyHostToDevice, ctx->stream));
-    int32_t* d_moves = e->d_i32 + G;
+    int32_t* d_moves = e->d_i32 + G; int32_t* d_rec = e->d_i32 + 2 * (size_t)G;
     std::vector<int32_t> prev = e->h_moves;
-    TG_LAUNCH(ctx, k_play, G, e->dev, (const int32_t*)d_act, e->d_u8, d_moves);
+    e->h_rec.resize(G);
+    TG_LAUNCH(ctx, k_play, G, e->dev, (const int32_t*)d_act, e->d_u8, d_moves, d_rec);
     hipLaunchKernelGGL(k_pool_publish, dim3(1), dim3(1), 0, ctx->stream, e->dev);      // the old trees' chunks are poppable from here on
     hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, ctx->stream, e->dev, e->R, 0);
     TG_HIP(ctx, hipGetLastError());
     TG_HIP(ctx, hipMemcpyAsync(done, e->d_u8, G, hipMemcpyDeviceToHost, ctx->stream));
     TG_HIP(ctx, hipMemcpyAsync(e->h_moves.data(), d_moves, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
+    TG_HIP(ctx, hipMemcpyAsync(e->h_rec.data(), d_rec, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
     int32_t cnt[CNT_N];
     int rc = read_counters(ctx, cnt);
     if (rc) return rc;
     e->batch_kind = BATCH_ROOTS; e->batch_ready = cnt[CNT_ROWS] == 0; e->last_rows = cnt[CNT_ROWS];
     e->n_errors = cnt[CNT_ERRORS];
-    // games this call finished (a slot that was already over does not move and is not listed again), ascending slot order
+    // games this call finished (a slot that was already over does not move and is not listed again), ascending slot order; a game
+    // contributes the plies it recorded (k_play counted them: all of its moves unless tg_sp_begin_move_games kept some out)
     e->fin_slot.clear(); e->fin_off.clear(); e->fin_positions = 0;
     for (int g = 0; g < G; ++g)
         if (done[g] == 1 && e->h_moves[g] == prev[g] + 1) {
-            const int n = e->h_moves[g] < e->dev.hist_T ? e->h_moves[g] : e->dev.hist_T;
+            const int cap = e->h_moves[g] < e->dev.hist_T ? e->h_moves[g] : e->dev.hist_T;
+            const int n = e->h_rec[g] < 0 ? 0 : e->h_rec[g] > cap ? cap : e->h_rec[g];
             e->fin_slot.push_back(g); e->fin_off.push_back(e->fin_positions); e->fin_positions += n;
         }
     return TG_OK;
@@ -1569,8 +1649,9 @@ int tg_sp_harvest(tg_ctx* ctx, uint32_t* obs_bits, int32_t* counts, float* z, in
     TG_HIP(ctx, hipMemcpyAsync(e->d_fin + e->G, e->fin_off.data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, ctx->stream));
     uint32_t* d_obs = obs_bits; int32_t* d_cnt = counts; float* d_z = z; int8_t* d_own = own; uint8_t* d_pl = player;
     if (!device_out) {
-        if (e->hv_obs.reserve(sizeof(uint32_t) * (size_t)np * W) || e->hv_cnt.reserve(sizeof(int32_t) * (size_t)np * A) ||
-            e->hv_z.reserve(sizeof(float) * (size_t)np) || e->hv_own.reserve((size_t)np * P) || e->hv_pl.reserve((size_t)np))
+        const size_t npa = np > 0 ? (size_t)np : 1;                    // games without a recorded position: no null staging pointers
+        if (e->hv_obs.reserve(sizeof(uint32_t) * npa * W) || e->hv_cnt.reserve(sizeof(int32_t) * npa * A) ||
+            e->hv_z.reserve(sizeof(float) * npa) || e->hv_own.reserve(npa * P) || e->hv_pl.reserve(npa))
             TG_FAIL(ctx, TG_ERR_HIP, "hipMalloc failed");
         d_obs = (uint32_t*)e->hv_obs.p; d_cnt = (int32_t*)e->hv_cnt.p; d_z = (float*)e->hv_z.p; d_own = (int8_t*)e->hv_own.p;
         d_pl = player ? (uint8_t*)e->hv_pl.p : nullptr;
@@ -1580,7 +1661,7 @@ int tg_sp_harvest(tg_ctx* ctx, uint32_t* obs_bits, int32_t* counts, float* z, in
     int32_t* d_w = (int32_t*)e->hv_game.p; float* d_s = (float*)(d_w + nf); int8_t* d_t = (int8_t*)(d_s + nf);
     TG_LAUNCH(ctx, k_harvest, nf, e->dev, (const int32_t*)e->d_fin, (const int32_t*)(e->d_fin + e->G), d_obs, d_cnt, d_z, d_own,
               d_pl, d_w, d_s, d_t);
-    if (!device_out) {
+    if (!device_out && np > 0) {
         TG_HIP(ctx, hipMemcpyAsync(obs_bits, d_obs, sizeof(uint32_t) * (size_t)np * W, hipMemcpyDeviceToHost, ctx->stream));
         TG_HIP(ctx, hipMemcpyAsync(counts, d_cnt, sizeof(int32_t) * (size_t)np * A, hipMemcpyDeviceToHost, ctx->stream));
         TG_HIP(ctx, hipMemcpyAsync(z, d_z, sizeof(float) * (size_t)np, hipMemcpyDeviceToHost, ctx->stream));

@@ -106,4 +106,16 @@ int tg_host_mt_dirichlet(tg_mt19937* s, double alpha, int32_t n, double* out) {
     return 0;
 }
 
+// Playout cap randomization: the draw that makes ply `ply` of the game seeded `seed` a full or a fast search.
+// Counter-based (the splitmix64 finaliser, twice), so it needs no state and leaves the game's MT19937 stream alone.
+static inline uint64_t cap_mix(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+uint32_t tg_host_cap_draw(uint32_t seed, int32_t ply, uint32_t cap_seed) {
+    return (uint32_t)(cap_mix(cap_mix(((uint64_t)cap_seed << 32) | seed) ^ (uint64_t)(uint32_t)ply) >> 40);
+}
+
 }  // extern "C"

@@ -230,7 +230,9 @@ std::string mismatch(const char* field, double snap, double mine) {
 }
 
 // Everything tg_sp_restore can check on the host: the tables of a snapshot whose header passed.  tab = the first tables_bytes.
-int validate_tables(tg_ctx* ctx, const SnapHdr& h, const uint8_t* tab) {
+// pl = the side-to-move section (one byte per recorded ply, games in slot order), which says how many positions a finished game
+// contributes: its plies without the kPlySkip mark.
+int validate_tables(tg_ctx* ctx, const SnapHdr& h, const uint8_t* tab, const uint8_t* pl) {
     const SearchCfg& sc = ctx->eng->dev.sc;
     const int G = h.n_games;
     const GameCtl* ctl = (const GameCtl*)(tab + h.sec[SEC_CTL].off);
@@ -242,8 +244,10 @@ int validate_tables(tg_ctx* ctx, const SnapHdr& h, const uint8_t* tab) {
     char msg[200];
     std::vector<uint8_t> seen((size_t)sc.pool_chunks, 0);
     uint64_t at = 0, plies = 0;
+    std::vector<uint64_t> ply_at((size_t)G + 1, 0);                    // where game g's plies start in the record sections
     for (int g = 0; g < G; ++g) {
         const GameCtl& c = ctl[g];
+        ply_at[g] = plies;
         if (c.cur < 0 || c.cur > 1 || c.n_chunks < 0 || c.n_chunks > sc.max_chunks || c.spare < -1 || c.spare >= sc.pool_chunks || c.root < 0 ||
             c.root >= sc.pool_slots || c.free_slot < 0 || c.free_slot > sc.pool_slots || c.moves < 0 || c.searching) {
             snprintf(msg, sizeof(msg), "tg_sp_restore: the control record of game %d is damaged", g);
@@ -290,7 +294,9 @@ int validate_tables(tg_ctx* ctx, const SnapHdr& h, const uint8_t* tab) {
         const int slot = fin[i], off = fin[h.n_fin + i];
         if (slot < 0 || slot >= G || (i > 0 && slot <= fin[i - 1]) || off != pos)
             TG_FAIL(ctx, TG_ERR_ARG, "tg_sp_restore: the table of finished games is damaged");
-        pos += ctl[slot].moves < h.hist_T ? ctl[slot].moves : h.hist_T;
+        const int n = ctl[slot].moves < h.hist_T ? ctl[slot].moves : h.hist_T;
+        if (h.record_games && pl) { for (int t = 0; t < n; ++t) pos += (pl[ply_at[slot] + t] & kPlySkip) ? 0 : 1; }
+        else if (h.record_games) pos += n;
     }
     if (pos != h.fin_positions) TG_FAIL(ctx, TG_ERR_ARG, "tg_sp_restore: the table of finished games is damaged");
     return TG_OK;
@@ -414,7 +420,20 @@ int tg_sp_restore(tg_ctx* ctx, const void* in, uint64_t bytes, int device_mem) {
         TG_HIP(ctx, hipStreamSynchronize(st));
         tab = tab_copy.data();
     }
-    int rc = validate_tables(ctx, h, tab);
+    // the finished games' position counts depend on their plies' marks: that section is read too (a byte per ply, and only when
+    // finished games wait in the snapshot)
+    std::vector<uint8_t> pl_copy;
+    const uint8_t* pl = nullptr;
+    if (h.n_fin > 0 && h.hist_plies) {
+        pl = (const uint8_t*)in + h.sec[SEC_HIST_PL].off;
+        if (device_mem) {
+            pl_copy.resize(h.sec[SEC_HIST_PL].bytes);
+            TG_HIP(ctx, hipMemcpyAsync(pl_copy.data(), pl, pl_copy.size(), hipMemcpyDeviceToHost, st));
+            TG_HIP(ctx, hipStreamSynchronize(st));
+            pl = pl_copy.data();
+        }
+    }
+    int rc = validate_tables(ctx, h, tab, pl);
     if (rc) return rc;
     // staging and scratch are allocated while a failure still leaves the context as it was
     const uint8_t* src = (const uint8_t*)in;
@@ -431,6 +450,7 @@ int tg_sp_restore(tg_ctx* ctx, const void* in, uint64_t bytes, int device_mem) {
     TG_HIP(ctx, hipMemcpyAsync(d.ring, sec(SEC_RING), h.sec[SEC_RING].bytes, hipMemcpyDeviceToDevice, st));
     TG_HIP(ctx, hipMemcpyAsync(d.counters, sec(SEC_COUNTERS), h.sec[SEC_COUNTERS].bytes, hipMemcpyDeviceToDevice, st));
     TG_HIP(ctx, hipMemcpyAsync(d.rng, sec(SEC_RNG), h.sec[SEC_RNG].bytes, hipMemcpyDeviceToDevice, st));
+    TG_HIP(ctx, hipMemsetAsync(d.ply_skip, 0, (size_t)e->G, st));      // a snapshot is a move boundary: no record switch is in flight
     int32_t *coff, *poff; int32_t tot[3];
     rc = run_scan(ctx, &coff, &poff, tot);                             // the offsets, from the control records just restored
     if (rc) return rc;

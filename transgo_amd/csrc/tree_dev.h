@@ -21,6 +21,11 @@ constexpr uint8_t F_OPEN = 1;      // real_expanded (self_play.py:62)
 constexpr uint8_t F_PRIOR32 = 2;   // prior holds a float32 value (NumPy scalar-kind ladder, SURVEY.md Note N)
 constexpr uint8_t F_PSEUDO = 4;    // pseudo-expanded in the current wave, evaluation pending (self_play.py:634-636)
 
+// A game's record holds the side to move of every ply as one byte (1 black, 2 white); this bit marks a ply that was played but is
+// not a training position (playout cap randomization, a fast search).  It exists inside hist_pl and the snapshot's copy of it only:
+// every read-out masks it.
+constexpr uint8_t kPlySkip = 0x80;
+
 struct alignas(16) NodeRec {       // Node_V, self_play.py:51-63
     double prior;                  // prior
     float w;                       // value_sum (float32, accumulated leaf->root)

@@ -235,10 +235,22 @@ class SelfPlayEngine:
         actions, _ = self.choose_moves(vis, steps, selfplay=False)
         return actions
 
-    def search(self, selfplay=True, num_simulation=0):
-        """The search part of get_action_probs (self_play.py:659-664)."""
+    def search(self, selfplay=True, num_simulation=0, noise=None, record=None):
+        """The search part of get_action_probs (self_play.py:659-664).  Per-game arrays select tg_sp_begin_move_games (playout cap
+        randomization): `noise` bool[G] = which games get root noise (default: all when selfplay, none otherwise; a game without
+        noise draws nothing from its stream), `num_simulation` int[G] = every game's own budget (<= 0: the configured one),
+        `record` bool[G] = False keeps the ply this move plays out of the game's training positions.  With none of them given
+        the call is tg_sp_begin_move, as ever."""
         t0 = time.perf_counter()
-        self.ctx.call("tg_sp_begin_move", 1 if selfplay else 0, num_simulation)
+        if noise is None and record is None and np.ndim(num_simulation) == 0:
+            self.ctx.call("tg_sp_begin_move", 1 if selfplay else 0, num_simulation)
+        else:
+            sims = np.ascontiguousarray(np.broadcast_to(np.asarray(num_simulation), (self.G,)), np.int32)
+            if noise is None:
+                noise = np.full(self.G, bool(selfplay))
+            nz = np.ascontiguousarray(np.broadcast_to(np.asarray(noise), (self.G,)) != 0, np.uint8)
+            rec = None if record is None else np.ascontiguousarray(np.broadcast_to(np.asarray(record), (self.G,)) != 0, np.uint8)
+            self.ctx.call("tg_sp_begin_move_games", _ptr(nz), _ptr(sims), _ptr(rec))
         self.begin_move_s += time.perf_counter() - t0
         if self.evaluator is None:
             w = ctypes.c_int32()
@@ -266,6 +278,12 @@ class SelfPlayEngine:
         vis = np.zeros((self.G, self.A), np.int32); st = np.zeros(self.G, np.int32)
         self.ctx.call("tg_sp_root_info", _ptr(vis), None, None, _ptr(st), None)
         return vis, st
+
+    def root_plies(self):
+        """Moves played so far in every slot's game (the state's step counter starts at 1, go_env.cc:67; a parked slot reads 0)."""
+        st = np.zeros(self.G, np.int32)
+        self.ctx.call("tg_sp_root_info", None, None, None, _ptr(st), None)
+        return np.maximum(st - 1, 0)
 
     # ---- tree read-out (analysis; reads only, legal between any two engine calls) ------------------------------------------
     CHILD_PRESENT, CHILD_OPEN, CHILD_PRIOR32, CHILD_WIN, CHILD_LOSS = 1, 2, 4, 8, 16        # TG_CHILD_* bits of "flags"

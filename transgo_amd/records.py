@@ -146,7 +146,8 @@ def from_records(recs, S, C):
     n = int(np.sum(n_moves)) if recs else 0
     bits = np.zeros((n, W * 32), np.uint8)
     if n:
-        bits[:, :C * P] = np.concatenate([np.asarray(r.observations, np.uint8).reshape(len(r.players), -1) for r in recs])
+        # (a game may hold no position at all: every one of its moves was a fast search of playout cap randomization)
+        bits[:, :C * P] = np.concatenate([np.asarray(r.observations, np.uint8).reshape(len(r.players), C * P) for r in recs])
     obs_bits = np.packbits(bits, axis=1, bitorder="little").view(np.uint32).reshape(n, W)
     counts = np.concatenate([np.asarray(r.visits, np.int32).reshape(-1, P + 1) for r in recs]) if n else np.zeros((0, P + 1), np.int32)
     player = np.concatenate([np.asarray(r.players, np.uint8) for r in recs]) if n else np.zeros(0, np.uint8)

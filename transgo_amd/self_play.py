@@ -13,6 +13,7 @@ import numpy as np
 
 from .engine import SelfPlayEngine
 from . import model as _model
+from . import playout_cap
 
 
 def _call(method, *args):
@@ -81,6 +82,7 @@ class BatchedSelfPlay:
     def __init__(self, config, n_games, device=0, rank=0, world=1, evaluator=None, arena_slots=0, seed_fn=None, pool_slots=0,
                  eval_cache_entries=None):
         self.config, self.G, self.rank, self.world = config, n_games, rank, world
+        playout_cap.check_config(config)                   # (attributes may have been set after Config() checked them)
         self.S = config.board_size
         self.filters = getattr(config, "num_features", 128)
         self.blocks = getattr(config, "num_blocks", 6)
@@ -101,6 +103,7 @@ class BatchedSelfPlay:
         self.games_started = np.zeros(n_games, np.int64)
         self.seeds = np.zeros(n_games, np.uint32)          # seed of the game now running in each slot
         self.moves_played = 0
+        self.full_moves = 0                                # with the playout cap on: moves that were full searches (= recorded positions)
         self.last_live = 0
         self.games_finished = 0
         self.games_dropped = 0                             # games abandoned because their tree outgrew the arena
@@ -184,7 +187,18 @@ class BatchedSelfPlay:
         eng = self.engine
         live = int((~eng.finished).sum())
         t0 = time.perf_counter()
-        eng.search(selfplay, num_simulation)
+        if selfplay and playout_cap.enabled(self.config):
+            # playout cap randomization: every game draws, from (its seed, its ply, the cap seed), whether this move is a full search
+            # (the budget, root noise, recorded) or a fast one (playout_cap_fast simulations, no noise, kept out of the record);
+            # the move itself is chosen with the self-play temperature either way
+            cfg = self.config
+            full = playout_cap.schedule(self.seeds, eng.root_plies(), cfg.playout_cap_p_full, cfg.playout_cap_seed)
+            sims = np.where(full, num_simulation if num_simulation > 0 else cfg.num_simulation, cfg.playout_cap_fast)
+            noise = np.ones(self.G, bool) if cfg.playout_cap_fast_noise else full
+            eng.search(True, sims, noise=noise, record=full)
+            self.full_moves += int((full & ~eng.finished).sum())
+        else:
+            eng.search(selfplay, num_simulation)
         t1 = time.perf_counter()
         vis, steps = eng.root_visits()
         actions, _ = eng.choose_moves(vis, steps, selfplay)
