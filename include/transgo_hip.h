@@ -225,6 +225,26 @@ int tg_sp_root_children(tg_ctx* ctx, int32_t* n /*[G][A]*/, int32_t* pending /*[
 int tg_sp_pv(tg_ctx* ctx, int depth, int32_t* action /*[G][depth]*/, int32_t* n /*[G][depth]*/, float* w /*[G][depth]*/,
              int32_t* len /*[G]*/);
 
+/* ---- forced playouts and policy target pruning (KataGo section 3.2; DESIGN.md 12, transgo_amd/forced_playouts.py) ------------
+ * k >= 0 (0 = off, the default; KataGo uses 2): while k > 0, a move that begins with root noise (tg_sp_begin_move with
+ * selfplay != 0, tg_sp_begin_move_games for the games with noise[g] != 0) is a *forced* move until its tg_sp_play: at the root a
+ * child with n >= 1 and n + pending < sqrt(k * prior * (root.n + root.pending)) is selected before any other, and the counts
+ * tg_sp_play records for the game are pruned -- every child but the most visited gives back up to floor(sqrt(k * prior * root.n))
+ * visits while its score, recomputed with the reduced count, stays below the most visited child's.  The tree keeps its statistics
+ * as searched.  Moves without noise, and everything with k = 0, are untouched.  k is context state: it is not part of a snapshot
+ * (set it again after tg_sp_restore); TG_ERR_ARG for k < 0 or not finite, TG_ERR_STATE while a leaf batch is pending.  The flag of
+ * a forced move ends with the game's tg_sp_play, however that call leaves the game; tg_sp_reset ends it for the slots it restarts
+ * (the other slots keep theirs), tg_sp_reset_from and tg_sp_restore for every slot. */
+int tg_sp_forced_playouts(tg_ctx* ctx, double k);
+int tg_sp_forced_playouts_get(tg_ctx* ctx, double* k);
+/* The root visit counts per action with the pruning applied for the games whose move in progress is a forced one (pruned_game[g]
+ * = 1), raw for every other game; all 0 for a game whose tg_sp_root_children status is not TG_ROOT_OK.  Meant for a search that
+ * is over (pending counters count as 0).  counts == 1 -> 0 (self_play.py:669) is the caller's step, as for tg_sp_root_info.
+ * A read-out like tg_sp_root_children: nothing changes.  Either pointer may be NULL: it is then neither computed nor copied. */
+int tg_sp_root_visits_pruned(tg_ctx* ctx, int32_t* visits /*[G][A] or NULL*/, uint8_t* pruned_game /*[G] or NULL*/);
+/* Cumulative since tg_create: root selections made in forced moves, and how many of them met at least one forced child. */
+int tg_sp_forced_playouts_stats(tg_ctx* ctx, uint64_t* root_selections, uint64_t* forced_selections);
+
 /* One random_sample() from each game's stream: the draw inside np.random.choice(A, p=) (self_play.py:683). */
 int tg_sp_draw_uniform(tg_ctx* ctx, double* u /*[G]*/, const uint8_t* mask);
 int tg_sp_rng_state(tg_ctx* ctx, int game, tg_mt19937* out);

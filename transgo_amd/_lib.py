@@ -59,6 +59,10 @@ SIGNATURES = {
     "tg_sp_root_info": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "tg_sp_root_children": (ctypes.c_int, [_vp] + [_vp] * 11),
     "tg_sp_pv": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "tg_sp_forced_playouts": (ctypes.c_int, [_vp, ctypes.c_double]),
+    "tg_sp_forced_playouts_get": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "tg_sp_root_visits_pruned": (ctypes.c_int, [_vp, _vp, _vp]),
+    "tg_sp_forced_playouts_stats": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "tg_sp_draw_uniform": (ctypes.c_int, [_vp, _vp, _vp]),
     "tg_sp_rng_state": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(TgMt19937)]),
     "tg_sp_rng_get": (ctypes.c_int, [_vp, _vp]),

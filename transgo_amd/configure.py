@@ -40,6 +40,8 @@ class Config:
         self.playout_cap_fast = 0                # simulations of a fast search (no root noise, not a training position); needed when p_full < 1
         self.playout_cap_seed = 0                # seed of the full / fast draws (a hash of game seed, ply and this; no game's RNG stream is used)
         self.playout_cap_fast_noise = False      # True: fast searches get root noise too.  Only p_full = 1.0 keeps parity with the reference
+        self.forced_playouts_k = 0.0             # > 0 (KataGo: 2.0): forced playouts and policy target pruning (transgo_amd/forced_playouts.py)
+                                                 # in every search that begins with root noise.  Only 0.0 keeps parity with the reference
         self.batch_size = 2048
         self.train_play_ratio = 7500 / 100000    # configure.py:61
         self.adjust_train_play_ratio = True
@@ -49,6 +51,8 @@ class Config:
             setattr(self, k, v)
         from .playout_cap import check_config
         check_config(self)
+        from .forced_playouts import check_k
+        check_k(self.forced_playouts_k)
 
     def epsilon_by_frame(self, game_step):       # configure.py:75-79
         return 0.65 + (1.0 - 0.65) * math.exp(-1. * game_step / 10)

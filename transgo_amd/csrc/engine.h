@@ -75,6 +75,11 @@ struct Engine {
     std::vector<int32_t> h_nchild;
     std::vector<int32_t> h_sims, h_rec;       // tg_sp_begin_move_games: the per-game budgets; tg_sp_play: recorded plies of the games it finished
     std::vector<uint8_t> h_flags;             // tg_sp_begin_move_games: noise switch [G] | skip switch [G]
+    // forced playouts: k is context state (0 = off: only then are k_collect_forced / k_play_forced launched); the
+    // per-game flag of a move in progress is set by k_begin, ended by k_play, cleared by every reset and restore
+    double forced_k = 0.0;
+    uint8_t* d_forced = nullptr;     // [G]  the move in progress began with root noise while k > 0
+    unsigned long long* d_forced_stat = nullptr;   // [2]  root selections of forced games, those that met a forced child
     Net* net = nullptr;
     EvalCache* cache = nullptr;      // tg_sp_eval_cache: nullptr = every pending row goes through the network (nothing else is launched)
     // HIP-event timing of the tree stage (k_collect, k_absorb) on the engine's stream, switched by tg_prof_enable

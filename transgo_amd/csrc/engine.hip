@@ -5,6 +5,7 @@
 // backups, feature encoding straight into the evaluation batch) and k_absorb (counter revert, prior renormalisation,
 // expansion, value backup).  Between the two the batch is evaluated by the network (net.hip) or, for parity tests,
 // by values injected through tg_sp_set_eval.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -86,6 +87,11 @@ __device__ __forceinline__ void pool_push(const EngineDev& d, const int32_t* ids
     base = ((unsigned long long)hi << 32) | lo;
     for (int i = lane; i < n; i += 64) d.ring[(base + i) % (unsigned long long)d.sc.pool_chunks] = ids[i];
     for (int i = lane; i < n2; i += 64) d.ring[(base + n + i) % (unsigned long long)d.sc.pool_chunks] = ids2[i];
+}
+// a masked reset ends the forced move (forced playouts) of the restarted slots only
+__global__ void k_clear_forced(uint8_t* forced, const uint8_t* mask, int n) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < n && mask[g]) forced[g] = 0;
 }
 // every chunk free (creation, and a reset of all games); the statistics survive a reset
 __global__ void k_pool_init(EngineDev d, int first) {
@@ -290,8 +296,11 @@ __global__ __launch_bounds__(64) void k_noise(EngineDev d, const double* noise, 
     }
 }
 
+// forced[g] (forced playouts): the move began with root noise while k > 0 (`force` = k > 0 and some game is noised;
+// noise_g = the per-game noise switches, nullptr = every game).  It lives until this move's k_play.
 template <int S>
-__global__ __launch_bounds__(64) void k_begin(EngineDev d, int sims, const int32_t* sims_g, const uint8_t* skip) {
+__global__ __launch_bounds__(64) void k_begin(EngineDev d, int sims, const int32_t* sims_g, const uint8_t* skip, uint8_t* forced,
+                                              const uint8_t* noise_g, int force) {
     const int g = blockIdx.x;
     if (lane_id() != 0) return;
     GameCtl* c = &d.ctl[g];
@@ -300,12 +309,15 @@ __global__ __launch_bounds__(64) void k_begin(EngineDev d, int sims, const int32
     c->n_target = d.arena[c->root].n + sims;                          // self_play.py:662-663
     c->searching = (c->finished || c->error) ? 0 : 1;
     c->active = c->searching;
+    forced[g] = (force && c->searching && (!noise_g || noise_g[g])) ? 1 : 0;
 }
 
-// 4096 boards = 16 single-wave workgroups per CU = 4 waves per SIMD: the register budget must let all of them be resident at once
-// (at 138 VGPRs only 12 fit and the kernel ran in two rounds).
-template <int S>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S == 9 ? 4 : 1))) void k_collect(EngineDev d) {
+// FORCED (forced playouts): the second instantiation, launched only while k > 0.  In a game whose move began with root
+// noise (forced[g]) a root child with n >= 1 and n + pending < sqrt(k * prior * (root.n + root.pending)) scores +inf; the maximum, the
+// tie list and the draw are what they are without it.  fstat[0] += root selections of forced games, fstat[1] += those that met a
+// forced child (reported only).  With FORCED = false the three extra parameters are dead (k_collect<9> keeps its resources).
+template <int S, bool FORCED>
+__device__ __forceinline__ void collect_body(const EngineDev d, const double fk, const uint8_t* forced, unsigned long long* fstat) {
     using G = Geo<S>;
     constexpr int HS = TreeGeo<S>::HS, NPASS = TreeGeo<S>::NPASS;
     __shared__ WaveLds<S> lds;
@@ -343,6 +355,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S == 9 ? 4 :
     int npaths = 0, err = 0;
     int leafs[8], rows[8];
     unsigned long long sims = 0, depth_sum = 0, evals = 0, child_sum = 0;
+    const bool fgame = FORCED && __builtin_amdgcn_readfirstlane((int)forced[g]) != 0;
+    int f_sel = 0, f_hit = 0;
     TG_ST_DECL;
 
     for (int attempt = 0; attempt < 2 * sc.R && npaths < sc.R && !err; ++attempt) {    // self_play.py:616
@@ -373,9 +387,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S == 9 ? 4 :
                 const int i = j * 64 + lane;
                 scv[j] = -INFINITY;
                 if (i < nchild) scv[j] = puct_score(ch[j], sq, sc);
+                if (FORCED && fgame && depth == 0 && i < nchild && ch[j].n >= 1 &&
+                    (double)(ch[j].n + ch[j].pending) < sqrt(fk * ch[j].prior * (double)(cur.n + cur.pending))) scv[j] = INFINITY;
                 best = scv[j] > best ? scv[j] : best;
             }
             best = wave_max(best);
+            if (FORCED && fgame && depth == 0) { ++f_sel; f_hit += best == INFINITY ? 1 : 0; }
             uint64_t tm[NPASS];
             int ntie = 0;
 #pragma unroll
@@ -468,7 +485,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S == 9 ? 4 :
         c->sims += sims; c->depth_sum += depth_sum; c->evals += evals; c->tie_draws += rng.draws; c->child_sum += child_sum;
         d.rng[g].pos = rng.pos;
         if (err) { atomicAdd(&d.counters[CNT_ERRORS], 1); c->searching = 0; c->active = 0; }
+        if (FORCED && f_sel) { atomicAdd(&fstat[0], (unsigned long long)f_sel); if (f_hit) atomicAdd(&fstat[1], (unsigned long long)f_hit); }
     }
+}
+
+// 4096 boards = 16 single-wave workgroups per CU = 4 waves per SIMD: the register budget must let all of them be resident at once
+// (at 138 VGPRs only 12 fit and the kernel ran in two rounds).
+template <int S>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S == 9 ? 4 : 1))) void k_collect(EngineDev d) {
+    collect_body<S, false>(d, 0.0, nullptr, nullptr);
+}
+template <int S>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S == 9 ? 4 : 1))) void k_collect_forced(EngineDev d, double fk, const uint8_t* forced,
+                                                                                                            unsigned long long* fstat) {
+    collect_body<S, true>(d, fk, forced, fstat);
 }
 
 template <int S>
@@ -592,6 +622,90 @@ __device__ __forceinline__ int root_status(const EngineDev& d, int g, NodeRec& r
     }
     if (blk < 0 || !(rec.flags & F_OPEN)) return TG_ROOT_UNEVALUATED;  // self_play.py:599-605 not done yet
     return TG_ROOT_OK;
+}
+
+// Policy target pruning (forced playouts; transgo_amd/forced_playouts.py is the definition).  One wave, a lane per
+// child, NPASS passes: act[j] / cnt[j] = action and pruned visit count of child j * 64 + lane (act -1: no such child).  c* = the
+// child with the most visits (ties: the lowest index = lowest action), S* = its score; every other visited child gives back up to
+// min(floor(sqrt(k * prior * root.n)), n) visits, one at a time, each only if the reduced count n' still scores below S* -- the
+// score with n' + 1 in the exploration term's denominator and q, the variance term at their final values, which is puct_score of
+// the record with pending = n' - n (so not one operation of puct_score differs).  Pending counters are taken as 0: the search is
+// over.  fk <= 0: the raw counts.  The tree is only read.
+template <int S>
+__device__ __forceinline__ void pruned_counts(const NodeRec* arena, const SearchCfg& sc, int root_n, int blk, int nchild, double fk,
+                                              int (&act)[TreeGeo<S>::NPASS], int (&cnt)[TreeGeo<S>::NPASS]) {
+    constexpr int HS = TreeGeo<S>::HS, NPASS = TreeGeo<S>::NPASS;
+    const int lane = lane_id();
+    NodeRec ch[NPASS];
+    unsigned long long key = 0;                                        // 0 = no child seen (a real key has ~index != 0 in its low word)
+#pragma unroll
+    for (int j = 0; j < NPASS; ++j) {
+        const int i = j * 64 + lane;
+        act[j] = -1; cnt[j] = 0;
+        ch[j].prior = 0.0; ch[j].w = 0.f; ch[j].var = 0.f; ch[j].n = 0; ch[j].pending = 0; ch[j].block = -1; ch[j].action = 0; ch[j].flags = 0; ch[j].term = 0;
+        if (i < nchild) {
+            ch[j] = arena[blk + HS + i];
+            act[j] = ch[j].action; cnt[j] = ch[j].n;
+            const unsigned long long k = ((unsigned long long)(uint32_t)(ch[j].n < 0 ? 0 : ch[j].n) << 32) | (uint32_t)~(uint32_t)i;
+            key = k > key ? k : key;
+        }
+    }
+    const unsigned long long best = wave_max_u64(key);
+    if ((best >> 32) == 0 || !(fk > 0.0)) return;                      // no child was visited, or pruning is off
+    const int bi = __builtin_amdgcn_readfirstlane((int)~(uint32_t)best);
+    NodeRec cs = ch[0];
+#pragma unroll
+    for (int j = 0; j < NPASS; ++j)
+        if ((bi >> 6) == j) cs = bcast_rec(ch[j], bi & 63);
+    cs.pending = 0;
+    const double sq = sqrt((double)root_n);
+    const double s_star = puct_score(cs, sq, sc);
+#pragma unroll
+    for (int j = 0; j < NPASS; ++j) {
+        const int i = j * 64 + lane;
+        if (i >= nchild || i == bi || ch[j].n < 1) continue;
+        const int n = ch[j].n;
+        const double fb = floor(sqrt(fk * ch[j].prior * (double)root_n));
+        const int lim = fb >= (double)n ? n : (int)fb;
+        NodeRec r = ch[j];
+        int m = n;
+        while (n - m < lim) {
+            r.pending = m - 1 - n;
+            if (!(puct_score(r, sq, sc) < s_star)) break;
+            --m;
+        }
+        cnt[j] = m;
+    }
+}
+
+// tg_sp_root_visits_pruned: the root visit counts per action, pruned for the games whose move in progress is a forced one (forced[g]
+// while fk > 0), raw for the others; rows of a game whose status is not TG_ROOT_OK are 0.  A read-out: every reference is checked.
+template <int S>
+__global__ __launch_bounds__(64) void k_root_visits_pruned(EngineDev d, double fk, const uint8_t* forced, int32_t* visits, uint8_t* pruned_game) {
+    using G = Geo<S>;
+    constexpr int NPASS = TreeGeo<S>::NPASS;
+    const int g = blockIdx.x, lane = lane_id();
+    const size_t row = (size_t)g * G::A;
+    if (visits) for (int a = lane; a < G::A; a += 64) visits[row + a] = 0;
+    NodeRec rec; rec.n = 0; rec.pending = 0; rec.w = 0.f; rec.var = 0.f; rec.flags = 0;
+    int blk;
+    const int st = root_status<S>(d, g, rec, blk);
+    bool pg = false;
+    if (st == TG_ROOT_OK) {
+        const int nchild = checked_nchild<S>(d.arena, d.sc, blk);
+        if (nchild >= 0) {
+            __syncthreads();                                           // the zeros are written before a child's entry is
+            pg = fk > 0.0 && __builtin_amdgcn_readfirstlane((int)forced[g]) != 0;
+        }
+        if (nchild >= 0 && visits) {
+            int act[NPASS], cnt[NPASS];
+            pruned_counts<S>(d.arena, d.sc, rec.n, blk, nchild, pg ? fk : 0.0, act, cnt);
+#pragma unroll
+            for (int j = 0; j < NPASS; ++j)
+                if (act[j] >= 0 && act[j] < G::A) visits[row + act[j]] = cnt[j];
+        }
+    }
+    if (lane == 0 && pruned_game) pruned_game[g] = pg ? 1 : 0;
 }
 
 // Dense per-action tables of the root's children + the root's own record (tg_sp_root_children).  Lanes go over the children in
@@ -721,8 +835,11 @@ __global__ __launch_bounds__(64) void k_tree_pv(EngineDev d, int D, int32_t* o_a
 // the side to move: what self_play.py:917-926 appends to its three Python lists.  A ply whose search was told not to record
 // (ply_skip, tg_sp_begin_move_games) is written all the same, with kPlySkip set in its side-to-move byte; for a game this move
 // finishes, rec_out = the number of its plies without the mark (the positions k_harvest will write).
-template <int S>
-__global__ __launch_bounds__(64) void k_play(EngineDev d, const int32_t* actions, uint8_t* done_out, int32_t* moves_out, int32_t* rec_out) {
+// FORCED (forced playouts; launched only while k > 0): the counts a forced game records are the pruned ones, and the
+// game's forced flag ends with the move.  The tree that is re-rooted keeps n, w and var as searched.
+template <int S, bool FORCED>
+__device__ __forceinline__ void play_body(const EngineDev& d, const int32_t* actions, uint8_t* done_out, int32_t* moves_out, int32_t* rec_out,
+                                          const double fk, uint8_t* forced) {
     using G = Geo<S>;
     constexpr int HS = TreeGeo<S>::HS, NPASS = TreeGeo<S>::NPASS;
     __shared__ WaveLds<S> lds;
@@ -732,6 +849,9 @@ __global__ __launch_bounds__(64) void k_play(EngineDev d, const int32_t* actions
     const int g = blockIdx.x, lane = lane_id();
     GameCtl* c = &d.ctl[g];
     const uint8_t skip = d.ply_skip[g];
+    // the forced flag ends with this call whichever way the kernel leaves: read once, cleared before the first exit
+    const bool fgame = FORCED && __builtin_amdgcn_readfirstlane((int)forced[g]) != 0;
+    if (FORCED && lane == 0) forced[g] = 0;
     if (lane == 0) { d.game_nslot[g] = 0; rec_out[g] = 0; }
     if (c->finished || c->error) { if (lane == 0) { done_out[g] = c->error ? 2 : 1; moves_out[g] = c->moves; } return; }
     const SearchCfg& sc = d.sc;
@@ -757,7 +877,15 @@ __global__ __launch_bounds__(64) void k_play(EngineDev d, const int32_t* actions
         int32_t* cnt = d.hist_cnt + e * G::A;
         for (int a2 = lane; a2 < G::A; a2 += 64) cnt[a2] = 0;
         __syncthreads();
-        for (int i = lane; i < nchild; i += 64) { NodeRec r = old[rblk + HS + i]; cnt[r.action] = r.n; }
+        if (FORCED && fgame) {
+            int pa[NPASS], pn[NPASS];
+            pruned_counts<S>(old, sc, old[c->root].n, rblk, nchild, fk, pa, pn);
+#pragma unroll
+            for (int j = 0; j < NPASS; ++j)
+                if (pa[j] >= 0) cnt[pa[j]] = pn[j];
+        } else {
+            for (int i = lane; i < nchild; i += 64) { NodeRec r = old[rblk + HS + i]; cnt[r.action] = r.n; }
+        }
         bw.load_colors(st.bb[0], st.bb[1]);
         bw.analyze();
         encode_bits<S, 2>(bw, st, d.rules, bits_s, d.hist_obs + e * d.obs_words);
@@ -891,6 +1019,16 @@ __global__ __launch_bounds__(64) void k_play(EngineDev d, const int32_t* actions
         done_out[g] = done ? 1 : 0; moves_out[g] = t + 1; rec_out[g] = rec;
         d.ply_skip[g] = 0;
     }
+}
+
+template <int S>
+__global__ __launch_bounds__(64) void k_play(EngineDev d, const int32_t* actions, uint8_t* done_out, int32_t* moves_out, int32_t* rec_out) {
+    play_body<S, false>(d, actions, done_out, moves_out, rec_out, 0.0, nullptr);
+}
+template <int S>
+__global__ __launch_bounds__(64) void k_play_forced(EngineDev d, const int32_t* actions, uint8_t* done_out, int32_t* moves_out, int32_t* rec_out,
+                                                    double fk, uint8_t* forced) {
+    play_body<S, true>(d, actions, done_out, moves_out, rec_out, fk, forced);
 }
 
 // Finished games -> training positions, on the device (self_play.py:929-967 minus the 8-fold augmentation, which the replay
@@ -1126,7 +1264,7 @@ int begin_move(tg_ctx* ctx, const char* who, bool noise_all, const uint8_t* nois
         TG_LAUNCH(ctx, k_noise, G, e->dev, (const double*)e->d_noise, d_noise_g);
     }
     { int rc = rng_to_device(ctx); if (rc) return rc; }
-    TG_LAUNCH(ctx, k_begin, G, e->dev, sims, d_sims, d_skip);
+    TG_LAUNCH(ctx, k_begin, G, e->dev, sims, d_sims, d_skip, e->d_forced, d_noise_g, (noise_all && e->forced_k > 0.0) ? 1 : 0);
     TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return TG_OK;
 }
@@ -1223,6 +1361,10 @@ int tg_engine_create(tg_ctx* ctx) {
     }
     TG_HIP(ctx, hipMalloc((void**)&e->dev.ply_skip, (size_t)G));
     TG_HIP(ctx, hipMemsetAsync(e->dev.ply_skip, 0, (size_t)G, ctx->stream));
+    TG_HIP(ctx, hipMalloc((void**)&e->d_forced, (size_t)G));
+    TG_HIP(ctx, hipMemsetAsync(e->d_forced, 0, (size_t)G, ctx->stream));
+    TG_HIP(ctx, hipMalloc((void**)&e->d_forced_stat, sizeof(unsigned long long) * 2));
+    TG_HIP(ctx, hipMemsetAsync(e->d_forced_stat, 0, sizeof(unsigned long long) * 2, ctx->stream));
     e->h_noise.resize((size_t)G * A);
     e->h_nchild.resize(G);
     e->arena_bytes = arena_bytes;
@@ -1251,7 +1393,7 @@ void tg_engine_destroy(tg_ctx* ctx) {
     if (!e) return;
     void* ptrs[] = {e->dev.arena, e->dev.ring, e->dev.pool, e->dev.chunk_ids, e->dev.ctl, e->dev.rng, e->dev.path_nodes, e->dev.path_len, e->dev.path_row, e->dev.row_slot,
                     e->dev.obs_bits, e->dev.game_nslot, e->dev.game_off, e->dev.game_act, e->dev.policy, e->dev.value, e->dev.counters, e->d_noise, e->d_i32, e->d_f32, e->d_u8,
-                    e->d_fin, e->dev.hist_obs, e->dev.hist_cnt, e->dev.hist_pl, e->dev.ply_skip};
+                    e->d_fin, e->dev.hist_obs, e->dev.hist_cnt, e->dev.hist_pl, e->dev.ply_skip, e->d_forced, e->d_forced_stat};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->h_rng) (void)hipHostFree(e->h_rng);
     e->obs_f32.release(); e->readout.release(); e->snap_tab.release(); e->snap_stage.release(); e->hv_obs.release(); e->hv_cnt.release(); e->hv_z.release(); e->hv_own.release(); e->hv_pl.release(); e->hv_game.release();
@@ -1286,6 +1428,9 @@ int tg_sp_reset(tg_ctx* ctx, const uint32_t* seeds, const uint8_t* mask) {
     if (g_trace_launch) { fprintf(stderr, "[tg %ld] k_reset<%d> grid %d (masked %d)\n", ++g_trace_seq, ctx->S, G, mask ? 1 : 0); fflush(stderr); }
     // every game at once: the ring is rebuilt with all chunks free and no game returns anything; a masked reset returns the
     // restarted games' chunks (poppable after the publish below)
+    // no restarted slot is inside a forced move (forced playouts); the flags of the other slots stay
+    if (!mask) { TG_HIP(ctx, hipMemsetAsync(e->d_forced, 0, (size_t)G, ctx->stream)); }
+    else hipLaunchKernelGGL(k_clear_forced, dim3((G + 255) / 256), dim3(256), 0, ctx->stream, e->d_forced, (const uint8_t*)d_mask, G);
     if (!mask) hipLaunchKernelGGL(k_pool_init, dim3(64), dim3(256), 0, ctx->stream, e->dev, 0);
     else {
         hipLaunchKernelGGL(k_release, dim3(G), dim3(64), 0, ctx->stream, e->dev, (const uint8_t*)d_mask);
@@ -1318,6 +1463,7 @@ int tg_sp_reset_from(tg_ctx* ctx, const void* states, const uint8_t* mask) {
     for (int g = 0; g < G; ++g) if (!mask || mask[g]) e->h_moves[g] = 0;
     e->fin_slot.clear(); e->fin_off.clear(); e->fin_positions = 0;
     TG_HIP(ctx, hipMemsetAsync(e->dev.ply_skip, 0, (size_t)G, ctx->stream));
+    TG_HIP(ctx, hipMemsetAsync(e->d_forced, 0, (size_t)G, ctx->stream));          // (every slot is restarted or parked)
     // (unmasked slots are parked by k_reset and keep the one chunk they own until their next reset)
     hipLaunchKernelGGL(k_release, dim3(G), dim3(64), 0, ctx->stream, e->dev, (const uint8_t*)d_mask);
     hipLaunchKernelGGL(k_pool_publish, dim3(1), dim3(1), 0, ctx->stream, e->dev);
@@ -1427,7 +1573,8 @@ int tg_sp_collect(tg_ctx* ctx, int32_t* n_active, int32_t* n_rows) {
     { int rc = rng_to_device(ctx); if (rc) return rc; }
     const bool timed = e->tprof && e->tev_used + 4 <= e->tev.size();
     if (timed) { TG_HIP(ctx, hipEventRecord(e->tev[e->tev_used], ctx->stream)); }
-    TG_LAUNCH(ctx, k_collect, e->G, e->dev);
+    if (e->forced_k > 0.0) TG_LAUNCH(ctx, k_collect_forced, e->G, e->dev, e->forced_k, (const uint8_t*)e->d_forced, e->d_forced_stat);
+    else TG_LAUNCH(ctx, k_collect, e->G, e->dev);
     hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, ctx->stream, e->dev, e->R, 1);
     TG_HIP(ctx, hipGetLastError());
     if (timed) { TG_HIP(ctx, hipEventRecord(e->tev[e->tev_used + 1], ctx->stream)); e->tev_kind[e->tev_used / 2] = 0; e->tev_used += 2; e->tree_waves++; }
@@ -1558,6 +1705,46 @@ int tg_sp_pv(tg_ctx* ctx, int depth, int32_t* action, int32_t* n, float* w, int3
     return TG_OK;
 }
 
+// ---- forced playouts and policy target pruning ---------------------------------------------------------------
+int tg_sp_forced_playouts(tg_ctx* ctx, double k) {
+    if (!ctx) return TG_ERR_ARG;
+    if (!ctx->eng || ctx->eng->G <= 0) TG_FAIL(ctx, TG_ERR_ARG, "tg_sp_forced_playouts: the context has no self-play engine (n_games = 0)");
+    if (!std::isfinite(k) || k < 0.0) TG_FAIL(ctx, TG_ERR_ARG, "tg_sp_forced_playouts: k must be a finite number >= 0 (0 = off)");
+    if (ctx->eng->batch_kind == BATCH_LEAVES) TG_FAIL(ctx, TG_ERR_STATE, "tg_sp_forced_playouts: an evaluation batch is pending");
+    ctx->eng->forced_k = k;
+    return TG_OK;
+}
+
+int tg_sp_forced_playouts_get(tg_ctx* ctx, double* k) {
+    if (!ctx || !ctx->eng || !k) return TG_ERR_ARG;
+    *k = ctx->eng->forced_k;
+    return TG_OK;
+}
+
+int tg_sp_root_visits_pruned(tg_ctx* ctx, int32_t* visits, uint8_t* pruned_game) {
+    NEED_READOUT(ctx, "tg_sp_root_visits_pruned");
+    Engine* e = ctx->eng;
+    const size_t G = (size_t)e->G, GA = G * ctx->A;
+    // staging: visits i32[G][A] | pruned_game u8[G]
+    if (e->readout.reserve(GA * 4 + G)) TG_FAIL(ctx, TG_ERR_HIP, "hipMalloc failed");
+    int32_t* d_vis = (int32_t*)e->readout.p; uint8_t* d_pg = (uint8_t*)(d_vis + GA);
+    TG_LAUNCH(ctx, k_root_visits_pruned, e->G, e->dev, e->forced_k, (const uint8_t*)e->d_forced, visits ? d_vis : (int32_t*)nullptr, d_pg);
+    if (visits) TG_HIP(ctx, hipMemcpyAsync(visits, d_vis, sizeof(int32_t) * GA, hipMemcpyDeviceToHost, ctx->stream));
+    if (pruned_game) TG_HIP(ctx, hipMemcpyAsync(pruned_game, d_pg, G, hipMemcpyDeviceToHost, ctx->stream));
+    TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return TG_OK;
+}
+
+int tg_sp_forced_playouts_stats(tg_ctx* ctx, uint64_t* root_selections, uint64_t* forced_selections) {
+    NEED_ENGINE(ctx);
+    unsigned long long h[2] = {0, 0};
+    TG_HIP(ctx, hipMemcpyAsync(h, ctx->eng->d_forced_stat, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (root_selections) *root_selections = h[0];
+    if (forced_selections) *forced_selections = h[1];
+    return TG_OK;
+}
+
 int tg_sp_draw_uniform(tg_ctx* ctx, double* u, const uint8_t* mask) {
     NEED_ENGINE(ctx);
     Engine* e = ctx->eng;
@@ -1606,7 +1793,8 @@ int tg_sp_play(tg_ctx* ctx, const int32_t* actions, uint8_t* done) {
     int32_t* d_moves = e->d_i32 + G; int32_t* d_rec = e->d_i32 + 2 * (size_t)G;
     std::vector<int32_t> prev = e->h_moves;
     e->h_rec.resize(G);
-    TG_LAUNCH(ctx, k_play, G, e->dev, (const int32_t*)d_act, e->d_u8, d_moves, d_rec);
+    if (e->forced_k > 0.0) TG_LAUNCH(ctx, k_play_forced, G, e->dev, (const int32_t*)d_act, e->d_u8, d_moves, d_rec, e->forced_k, e->d_forced);
+    else TG_LAUNCH(ctx, k_play, G, e->dev, (const int32_t*)d_act, e->d_u8, d_moves, d_rec);
     hipLaunchKernelGGL(k_pool_publish, dim3(1), dim3(1), 0, ctx->stream, e->dev);      // the old trees' chunks are poppable from here on
     hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, ctx->stream, e->dev, e->R, 0);
     TG_HIP(ctx, hipGetLastError());

@@ -113,7 +113,7 @@ class SelfPlayEngine:
     def __init__(self, n_games, board_size=9, num_simulation=210, parallel_readouts=4, c_puct1=3, c_puct2=0.05,
                  wu_loss=2, komi=7.5, max_step=120, encode_dim=10, net_blocks=6, net_filters=128, arena_slots=0,
                  device=0, evaluator=None, net_precision="f32", record_games=True, pool_slots=0, eval_symmetry="none",
-                 symmetry_seed=0, eval_cache_entries=0):
+                 symmetry_seed=0, eval_cache_entries=0, forced_playouts_k=0.0):
         cfg = _lib.default_config()
         cfg.record_games = 1 if record_games else 0       # per-move records in HBM for tg_sp_harvest (self-play); evaluation matches need none
         cfg.net_precision = {"f32": 0, "f16": 1, "f16r": 2, "f32x3": 3}[net_precision]
@@ -136,6 +136,9 @@ class SelfPlayEngine:
             self.set_symmetry(eval_symmetry, symmetry_seed)
         if eval_cache_entries:
             self.set_eval_cache(eval_cache_entries)
+        self.forced_playouts_k = 0.0
+        if forced_playouts_k:
+            self.set_forced_playouts(forced_playouts_k)
 
     def close(self):
         self.ctx.close()
@@ -176,6 +179,27 @@ class SelfPlayEngine:
     def eval_cache_stats(self):
         """tg_sp_eval_cache_stats as a dict (EVAL_CACHE_STATS): cumulative since the cache was created, all 0 without one."""
         return eval_cache_stats(self)
+
+    # ---- forced playouts and policy target pruning (tg_sp_forced_playouts; DESIGN.md 12) ------------------------------------
+    def set_forced_playouts(self, k):
+        """k > 0 (KataGo: 2.0): a search that begins with root noise forces every visited root child up to sqrt(k * prior * N)
+        visits, and the counts that become the pi target and the move choice are pruned of the visits that were only forced
+        (transgo_amd.forced_playouts holds the definition).  0.0 = off.  Context state: a restored snapshot does not carry it."""
+        from . import forced_playouts as _fp
+        k = _fp.check_k(k)
+        self.ctx.call("tg_sp_forced_playouts", ctypes.c_double(k))
+        self.forced_playouts_k = k
+
+    def get_forced_playouts(self):
+        k = ctypes.c_double()
+        self.ctx.call("tg_sp_forced_playouts_get", ctypes.byref(k))
+        return float(k.value)
+
+    def forced_playouts_stats(self):
+        """Root selections made in forced moves so far, and how many of them met a forced child."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self.ctx.call("tg_sp_forced_playouts_stats", ctypes.byref(a), ctypes.byref(b))
+        return dict(root_selections=int(a.value), forced_selections=int(b.value))
 
     # ---- evaluation of the pending batch --------------------------------------------------------------------------------
     def _evaluate(self, rows=None):
@@ -273,11 +297,23 @@ class SelfPlayEngine:
         self.ctx.call("tg_sp_root_info", _ptr(vis), _ptr(rn), _ptr(pl), _ptr(st), _ptr(ob))
         return vis, rn, pl, st, ob
 
-    def root_visits(self):
-        """Visit counts and ply counters only (what move selection needs): 4*(A+1) bytes per game across PCIe."""
+    def root_visits(self, pruned=False):
+        """Visit counts and ply counters only (what move selection needs): 4*(A+1) bytes per game across PCIe.  pruned=True
+        (tg_sp_root_visits_pruned): the games whose move in progress is a forced one (forced playouts) report their pruned counts,
+        every other game its raw ones -- what choose_moves is fed with while forced_playouts_k > 0."""
         vis = np.zeros((self.G, self.A), np.int32); st = np.zeros(self.G, np.int32)
-        self.ctx.call("tg_sp_root_info", _ptr(vis), None, None, _ptr(st), None)
+        if pruned:
+            self.ctx.call("tg_sp_root_info", None, None, None, _ptr(st), None)
+            self.ctx.call("tg_sp_root_visits_pruned", _ptr(vis), None)
+        else:
+            self.ctx.call("tg_sp_root_info", _ptr(vis), None, None, _ptr(st), None)
         return vis, st
+
+    def pruned_games(self):
+        """bool[G]: the games tg_sp_root_visits_pruned prunes right now (their move began with root noise while k > 0)."""
+        pg = np.zeros(self.G, np.uint8)
+        self.ctx.call("tg_sp_root_visits_pruned", None, _ptr(pg))
+        return pg != 0
 
     def root_plies(self):
         """Moves played so far in every slot's game (the state's step counter starts at 1, go_env.cc:67; a parked slot reads 0)."""

@@ -98,7 +98,8 @@ class BatchedSelfPlay:
             pool_slots=pool_slots or getattr(config, "tree_pool_slots", 0),
             net_precision=getattr(config, "inference_dtype", "f32"),
             eval_symmetry=getattr(config, "eval_symmetry", "none"), symmetry_seed=getattr(config, "symmetry_seed", 0),
-            eval_cache_entries=getattr(config, "eval_cache_entries", 0) if eval_cache_entries is None else eval_cache_entries)
+            eval_cache_entries=getattr(config, "eval_cache_entries", 0) if eval_cache_entries is None else eval_cache_entries,
+            forced_playouts_k=getattr(config, "forced_playouts_k", 0.0))
         self.seed_fn = seed_fn
         self.games_started = np.zeros(n_games, np.int64)
         self.seeds = np.zeros(n_games, np.uint32)          # seed of the game now running in each slot
@@ -200,7 +201,9 @@ class BatchedSelfPlay:
         else:
             eng.search(selfplay, num_simulation)
         t1 = time.perf_counter()
-        vis, steps = eng.root_visits()
+        # forced playouts: the games whose move was a noised one choose from their pruned counts (with the playout cap on these are
+        # the full plies); every other game, and every game while k = 0, from the raw ones
+        vis, steps = eng.root_visits(pruned=True) if eng.forced_playouts_k > 0.0 else eng.root_visits()
         actions, _ = eng.choose_moves(vis, steps, selfplay)
         t2 = time.perf_counter()
         done = eng.play(actions)
@@ -253,6 +256,7 @@ class BatchedSelfPlay:
     def _restore_part(self, state, snap):
         self._check_part(state, snap)
         self.engine.restore(snap)                                      # refuses a mismatched geometry before it changes anything
+        self.engine.set_forced_playouts(getattr(self.config, "forced_playouts_k", 0.0))      # context state, not part of a snapshot
         self.games_started = np.asarray(state["games_started"], np.int64)
         self.seeds = np.asarray(state["seeds"], np.uint32)
         self.moves_played, self.games_finished = int(state["moves_played"]), int(state["games_finished"])
@@ -477,9 +481,12 @@ class WP_MCTS:
 
     def get_action_probs(self, is_selfplay=True, now_train_step=0):
         """self_play.py:657-687 -> (action, pi, encode(root)): root noise if is_selfplay, num_simulation more visits at the root,
-        counts == 1 -> 0, temperature schedule (0.12 when not self-play), np.random.choice."""
+        counts == 1 -> 0, temperature schedule (0.12 when not self-play), np.random.choice.  With Config.forced_playouts_k > 0 a
+        self-play search is a forced one, and the move and pi come from the pruned counts -- the counts update_with_action records."""
         self.engine.search(selfplay=bool(is_selfplay))
         vis, _, _, steps, obs = self.engine.root_info()
+        if self.engine.forced_playouts_k > 0.0:
+            vis = self.engine.root_visits(pruned=True)[0]
         actions, pis = self.engine.choose_moves(vis, steps, selfplay=bool(is_selfplay))
         return int(actions[0]), pis[0], obs[0]
 
