@@ -245,6 +245,37 @@ int tg_sp_root_visits_pruned(tg_ctx* ctx, int32_t* visits /*[G][A] or NULL*/, ui
 /* Cumulative since tg_create: root selections made in forced moves, and how many of them met at least one forced child. */
 int tg_sp_forced_playouts_stats(tg_ctx* ctx, uint64_t* root_selections, uint64_t* forced_selections);
 
+/* ---- Gumbel root search (Danihelka et al., ICLR 2022; DESIGN.md 13, transgo_amd/gumbel.py) -------------------------------------
+ * m >= 0 considered actions (0 = off, the default), c_visit, c_scale (the paper: 50, 1).  While m > 0, a move that would begin
+ * with root noise (tg_sp_begin_move with selfplay != 0, tg_sp_begin_move_games for the games with noise[g] != 0) is a *Gumbel
+ * move* until its tg_sp_play, and gets NO Dirichlet noise.  At its start the host takes one random_sample() u per root child
+ * (ascending action, pass last) from the game's stream: g = -log(-log(u)), gl = g + log((double)prior); the m_eff = min(m, nchild)
+ * children with the largest gl (ties: the lower action) are considered, every other child's gl is -inf.  The device stores
+ * n0[c] = c.n and N0 = root.n.  With wu the WU-UCT loss, e(c) = (c.n - n0[c]) + c.pending / wu and
+ * t = (root.n - N0) + root.pending / wu.  Root selection (depth 0 only): the considered children with e(c) == v(t), v the
+ * sequential-halving schedule for (m_eff, budget = n_target - N0) at step min(t, budget - 1) (gumbel.considered_visit); if none,
+ * the considered children with the smallest e(c) (counted as a fallback).  score(c) = gl[c] + (c_visit + maxN) * c_scale * qhat(c)
+ * in float64, maxN = the largest c.n over all root children, qhat(c) = (double)(-(c.w / (c.n + 1))) in float32; the maximum, the
+ * tie list in ascending action order and the one choice over it are the plain search's.  Moves without noise, and everything with
+ * m = 0, are untouched.  The parameters are context state: not part of a snapshot (set them again after tg_sp_restore).
+ * TG_ERR_ARG for m < 0, constants that are not finite, or m > 0 while forced playouts are on (tg_sp_forced_playouts refuses
+ * k > 0 while m > 0 in turn); TG_ERR_STATE while a leaf batch is pending.  The flag of a Gumbel move ends like a forced move's. */
+int tg_sp_gumbel(tg_ctx* ctx, int m, double c_visit, double c_scale);
+int tg_sp_gumbel_get(tg_ctx* ctx, int* m, double* c_visit, double* c_scale);
+/* The move of every game inside a Gumbel move whose search is over: argmax score(c) over the considered children with the largest
+ * e(c) (pending counts as 0), ties to the lower action; no draw.  action[g] = -1 and gumbel_game[g] = 0 for every other game (and
+ * for a game whose tg_sp_root_children status is not TG_ROOT_OK).  A read-out: nothing changes.  Either pointer may be NULL. */
+int tg_sp_gumbel_move(tg_ctx* ctx, int32_t* action /*[G] or NULL*/, uint8_t* gumbel_game /*[G] or NULL*/);
+/* The gl table of the moves in progress as uploaded, row g indexed by CHILD (ascending action order, nchild entries); rows of games
+ * that are not in a Gumbel move are unspecified.  TG_ERR_STATE while m = 0. */
+int tg_sp_gumbel_table(tg_ctx* ctx, double* gl /*[G][A]*/);
+/* Stages the counts tg_sp_play records for the games in a Gumbel move with mask[g] != 0 (NULL: all of them) in place of the visit
+ * counts: the improved policy as round_half_up(pi' * 2^24) (gumbel.improved_policy / fixed_point).  Every call replaces the
+ * staging of every game; a Gumbel game without staged counts records its raw visits.  TG_ERR_STATE while m = 0. */
+int tg_sp_gumbel_target(tg_ctx* ctx, const int32_t* counts /*[G][A]*/, const uint8_t* mask /*[G] or NULL*/);
+/* Cumulative since tg_create: root selections made in Gumbel moves, and how many of them found no child at v(t). */
+int tg_sp_gumbel_stats(tg_ctx* ctx, uint64_t* root_selections, uint64_t* fallback_selections);
+
 /* One random_sample() from each game's stream: the draw inside np.random.choice(A, p=) (self_play.py:683). */
 int tg_sp_draw_uniform(tg_ctx* ctx, double* u /*[G]*/, const uint8_t* mask);
 int tg_sp_rng_state(tg_ctx* ctx, int game, tg_mt19937* out);
@@ -476,6 +507,7 @@ uint32_t tg_host_mt_next32(tg_mt19937* s);
 double tg_host_mt_random_sample(tg_mt19937* s);                     /* random_sample(): the draw inside choice(A, p=) (self_play.py:683) */
 int32_t tg_host_mt_choice_index(tg_mt19937* s, int32_t k);          /* index drawn by choice(list of k) (self_play.py:709) */
 int tg_host_mt_dirichlet(tg_mt19937* s, double alpha, int32_t n, double* out);   /* dirichlet([alpha]*n) (self_play.py:93) */
+void tg_host_mt_gumbel(tg_mt19937* s, int32_t n, double* out);   /* n draws of -log(-log(random_sample())), libm's log */
 /* Playout cap randomization: the 24-bit draw that decides whether ply `ply` of the game seeded `seed` is searched in full --
  * mix(mix(cap_seed << 32 | seed) ^ ply) >> 40 with mix = the splitmix64 finaliser; full when draw < floor(p_full * 2^24).  A
  * pure function of its arguments: no game's MT19937 stream is touched (transgo_amd/playout_cap.py is the same in NumPy). */

@@ -63,6 +63,12 @@ SIGNATURES = {
     "tg_sp_forced_playouts_get": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "tg_sp_root_visits_pruned": (ctypes.c_int, [_vp, _vp, _vp]),
     "tg_sp_forced_playouts_stats": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "tg_sp_gumbel": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, ctypes.c_double]),
+    "tg_sp_gumbel_get": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    "tg_sp_gumbel_move": (ctypes.c_int, [_vp, _vp, _vp]),
+    "tg_sp_gumbel_table": (ctypes.c_int, [_vp, _vp]),
+    "tg_sp_gumbel_target": (ctypes.c_int, [_vp, _vp, _vp]),
+    "tg_sp_gumbel_stats": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "tg_sp_draw_uniform": (ctypes.c_int, [_vp, _vp, _vp]),
     "tg_sp_rng_state": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(TgMt19937)]),
     "tg_sp_rng_get": (ctypes.c_int, [_vp, _vp]),
@@ -118,6 +124,7 @@ SIGNATURES = {
     "tg_host_mt_choice_index": (ctypes.c_int32, [ctypes.POINTER(TgMt19937), ctypes.c_int32]),
     "tg_host_sub_encode": (None, [ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "tg_host_mt_dirichlet": (ctypes.c_int, [ctypes.POINTER(TgMt19937), ctypes.c_double, ctypes.c_int32, _vp]),
+    "tg_host_mt_gumbel": (None, [ctypes.POINTER(TgMt19937), ctypes.c_int32, _vp]),
     "tg_host_cap_draw": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32]),
 }
 

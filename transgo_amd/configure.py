@@ -42,6 +42,11 @@ class Config:
         self.playout_cap_fast_noise = False      # True: fast searches get root noise too.  Only p_full = 1.0 keeps parity with the reference
         self.forced_playouts_k = 0.0             # > 0 (KataGo: 2.0): forced playouts and policy target pruning (transgo_amd/forced_playouts.py)
                                                  # in every search that begins with root noise.  Only 0.0 keeps parity with the reference
+        self.gumbel_m = 0                        # > 0: Gumbel root search (transgo_amd/gumbel.py) with this many considered actions in
+                                                 # every search that would begin with root noise: sequential halving at the root, the
+                                                 # improved policy as the target.  Only 0 keeps parity with the reference
+        self.gumbel_c_visit = 50.0               # sigma(q) = (c_visit + max visits) * c_scale * q
+        self.gumbel_c_scale = 1.0
         self.batch_size = 2048
         self.train_play_ratio = 7500 / 100000    # configure.py:61
         self.adjust_train_play_ratio = True
@@ -53,6 +58,10 @@ class Config:
         check_config(self)
         from .forced_playouts import check_k
         check_k(self.forced_playouts_k)
+        from .gumbel import check_params
+        check_params(self.gumbel_m, self.gumbel_c_visit, self.gumbel_c_scale)
+        if self.gumbel_m > 0 and self.forced_playouts_k > 0:
+            raise ValueError("gumbel_m > 0 and forced_playouts_k > 0: both are rules for the same root, choose one")
 
     def epsilon_by_frame(self, game_step):       # configure.py:75-79
         return 0.65 + (1.0 - 0.65) * math.exp(-1. * game_step / 10)

@@ -80,6 +80,18 @@ struct Engine {
     double forced_k = 0.0;
     uint8_t* d_forced = nullptr;     // [G]  the move in progress began with root noise while k > 0
     unsigned long long* d_forced_stat = nullptr;   // [2]  root selections of forced games, those that met a forced child
+    // Gumbel root search: m, c_visit, c_scale are context state (m = 0: off, no *_gumbel kernel is launched).  The
+    // per-game flag has the forced flag's lifetime; the tables of a move are allocated when m is first set above 0.  The gl table
+    // itself travels through d_noise / h_noise, which a Gumbel move leaves idle.
+    int gumbel_m = 0;
+    double gumbel_c_visit = 50.0, gumbel_c_scale = 1.0;
+    uint8_t* d_gumbel = nullptr;     // [G]  the move in progress is a Gumbel move
+    unsigned long long* d_gumbel_stat = nullptr;   // [2]  root selections of Gumbel games, those that fell back to the smallest effort
+    int32_t* d_gumbel_n0 = nullptr;  // [G][A] by child index: c.n at the start of the move
+    int32_t* d_gumbel_N0 = nullptr;  // [G]    root.n at the start of the move
+    int32_t* d_gumbel_target = nullptr;   // [G][A] by action: the counts staged by tg_sp_gumbel_target
+    uint8_t* d_gumbel_staged = nullptr;   // [G]    ... and for which games
+    std::vector<double> h_gumbel;    // [G][A] the variates of one move (host)
     Net* net = nullptr;
     EvalCache* cache = nullptr;      // tg_sp_eval_cache: nullptr = every pending row goes through the network (nothing else is launched)
     // HIP-event timing of the tree stage (k_collect, k_absorb) on the engine's stream, switched by tg_prof_enable

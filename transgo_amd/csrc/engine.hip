@@ -5,6 +5,7 @@
 // backups, feature encoding straight into the evaluation batch) and k_absorb (counter revert, prior renormalisation,
 // expansion, value backup).  Between the two the batch is evaluated by the network (net.hip) or, for parity tests,
 // by values injected through tg_sp_set_eval.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -312,12 +313,51 @@ __global__ __launch_bounds__(64) void k_begin(EngineDev d, int sims, const int32
     forced[g] = (force && c->searching && (!noise_g || noise_g[g])) ? 1 : 0;
 }
 
+// Gumbel root search: the root children's priors as stored (float32 values for a fresh or re-rooted root), by child
+// index, and the child count (0 for a game that takes no part) -- what the host needs for gl = g + log(prior).
+template <int S>
+__global__ __launch_bounds__(64) void k_root_priors(EngineDev d, double* prior, int32_t* nchild_out) {
+    constexpr int HS = TreeGeo<S>::HS;
+    const int g = blockIdx.x, lane = lane_id();
+    const GameCtl* c = &d.ctl[g];
+    if (c->finished || c->error) { if (lane == 0) nchild_out[g] = 0; return; }
+    const NodeRec* arena = d.arena;
+    const int blk = arena[c->root].block;
+    const int nchild = hdr_of<S>(d.arena, blk)->nchild;
+    for (int i = lane; i < nchild && i < d.sc.A; i += 64) prior[(size_t)g * d.sc.A + i] = arena[blk + HS + i].prior;
+    if (lane == 0) nchild_out[g] = nchild;
+}
+// k_begin's sibling, launched behind it while m > 0 and some game would be noised: gflag[g] = the move is a Gumbel move (it lives
+// until this move's k_play, like forced[g]); n0 / N0 = the base counts (tree reuse leaves old visits at the root).
+template <int S>
+__global__ __launch_bounds__(64) void k_begin_gumbel(EngineDev d, uint8_t* gflag, const uint8_t* noise_g, int32_t* n0, int32_t* N0, uint8_t* gstaged) {
+    constexpr int HS = TreeGeo<S>::HS;
+    const int g = blockIdx.x, lane = lane_id();
+    const GameCtl* c = &d.ctl[g];
+    const bool on = c->searching && (!noise_g || noise_g[g]);
+    if (lane == 0) { gflag[g] = on ? 1 : 0; gstaged[g] = 0; }          // nothing is staged for a move that has not been searched
+    if (!on) return;
+    const NodeRec* arena = d.arena;
+    const NodeRec root = arena[c->root];
+    const int nchild = hdr_of<S>(d.arena, root.block)->nchild;
+    for (int i = lane; i < nchild && i < d.sc.A; i += 64) n0[(size_t)g * d.sc.A + i] = arena[root.block + HS + i].n;
+    if (lane == 0) N0[g] = root.n;
+}
+
+// MODE: COLLECT_PLAIN is the reference's search; the other two are further instantiations, each launched only
+// while its feature is on, with the parameters of the absent rules dead (k_collect<9> keeps its resources).
+enum { COLLECT_PLAIN = 0, COLLECT_FORCED = 1, COLLECT_GUMBEL = 2 };
 // FORCED (forced playouts): the second instantiation, launched only while k > 0.  In a game whose move began with root
 // noise (forced[g]) a root child with n >= 1 and n + pending < sqrt(k * prior * (root.n + root.pending)) scores +inf; the maximum, the
 // tie list and the draw are what they are without it.  fstat[0] += root selections of forced games, fstat[1] += those that met a
 // forced child (reported only).  With FORCED = false the three extra parameters are dead (k_collect<9> keeps its resources).
-template <int S, bool FORCED>
-__device__ __forceinline__ void collect_body(const EngineDev d, const double fk, const uint8_t* forced, unsigned long long* fstat) {
+// GUMBEL (Gumbel root search): in a game whose move is a Gumbel move (gd.flag[g]) the root level selects among the
+// considered children (gl > -inf) whose effort e(c) equals the schedule's v(t) -- if there are none, those with the smallest e(c),
+// counted in gd.stat[1] -- by score(c) = gl[c] + (c_visit + maxN) * c_scale * qhat(c); the tie list and the draw are the plain ones.
+template <int S, int MODE>
+__device__ __forceinline__ void collect_body(const EngineDev d, const double fk, const uint8_t* forced, unsigned long long* fstat,
+                                             const GumbelDev gd) {
+    constexpr bool FORCED = MODE == COLLECT_FORCED, GUMBEL = MODE == COLLECT_GUMBEL;
     using G = Geo<S>;
     constexpr int HS = TreeGeo<S>::HS, NPASS = TreeGeo<S>::NPASS;
     __shared__ WaveLds<S> lds;
@@ -357,6 +397,16 @@ __device__ __forceinline__ void collect_body(const EngineDev d, const double fk,
     unsigned long long sims = 0, depth_sum = 0, evals = 0, child_sum = 0;
     const bool fgame = FORCED && __builtin_amdgcn_readfirstlane((int)forced[g]) != 0;
     int f_sel = 0, f_hit = 0;
+    bool ggame = false;
+    int g_N0 = 0, g_budget = 1;
+    if constexpr (GUMBEL) {
+        ggame = __builtin_amdgcn_readfirstlane((int)gd.flag[g]) != 0;
+        if (ggame) {
+            g_N0 = __builtin_amdgcn_readfirstlane(gd.N0[g]);
+            g_budget = __builtin_amdgcn_readfirstlane(c->n_target) - g_N0;
+            g_budget = g_budget < 1 ? 1 : g_budget;
+        }
+    }
     TG_ST_DECL;
 
     for (int attempt = 0; attempt < 2 * sc.R && npaths < sc.R && !err; ++attempt) {    // self_play.py:616
@@ -382,8 +432,42 @@ __device__ __forceinline__ void collect_body(const EngineDev d, const double fk,
             const double sq = sqrt((double)(cur.n + cur.pending));
             double scv[NPASS];
             double best = -INFINITY;
+            bool el[NPASS];                                            // GUMBEL: the child is eligible at this root selection
+            const bool groot = GUMBEL && ggame && depth == 0;
+            if constexpr (GUMBEL) {
+                if (groot) {
+                    const int t = (cur.n - g_N0) + (sc.wu > 0 ? cur.pending / sc.wu : 0);
+                    const int v = considered_visit(gd.m < nchild ? gd.m : nchild, g_budget, t);
+                    double glv[NPASS]; int ev[NPASS];
+                    int maxn = 0, mine = 0x7fffffff;
+                    uint64_t any = 0;
 #pragma unroll
-            for (int j = 0; j < NPASS; ++j) {
+                    for (int j = 0; j < NPASS; ++j) {
+                        const int i = j * 64 + lane;
+                        glv[j] = -INFINITY; ev[j] = 0;
+                        if (i < nchild) {
+                            glv[j] = gd.gl[(size_t)g * sc.A + i];
+                            ev[j] = gumbel_effort(ch[j], gd.n0[(size_t)g * sc.A + i], sc.wu);
+                            maxn = ch[j].n > maxn ? ch[j].n : maxn;
+                            if (glv[j] > -INFINITY) mine = ev[j] < mine ? ev[j] : mine;
+                        }
+                        any |= ballot64(glv[j] > -INFINITY && ev[j] == v);
+                    }
+                    maxn = wave_max_i32(maxn); mine = wave_min_i32(mine);
+                    const int want = any ? v : mine;
+                    const double mult = (gd.c_visit + (double)maxn) * gd.c_scale;
+#pragma unroll
+                    for (int j = 0; j < NPASS; ++j) {
+                        el[j] = glv[j] > -INFINITY && ev[j] == want;
+                        scv[j] = -INFINITY;
+                        if (el[j]) scv[j] = gumbel_score(glv[j], mult, ch[j]);
+                        best = scv[j] > best ? scv[j] : best;
+                    }
+                    ++f_sel; f_hit += any ? 0 : 1;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < NPASS && !groot; ++j) {
                 const int i = j * 64 + lane;
                 scv[j] = -INFINITY;
                 if (i < nchild) scv[j] = puct_score(ch[j], sq, sc);
@@ -396,7 +480,7 @@ __device__ __forceinline__ void collect_body(const EngineDev d, const double fk,
             uint64_t tm[NPASS];
             int ntie = 0;
 #pragma unroll
-            for (int j = 0; j < NPASS; ++j) { tm[j] = ballot64(scv[j] == best); ntie += __popcll(tm[j]); }
+            for (int j = 0; j < NPASS; ++j) { tm[j] = ballot64(groot ? (el[j] && scv[j] == best) : scv[j] == best); ntie += __popcll(tm[j]); }
             int k = (ntie > 1) ? rng.choice_index(ntie) : 0;
             int idx = 0;
 #pragma unroll
@@ -486,6 +570,7 @@ __device__ __forceinline__ void collect_body(const EngineDev d, const double fk,
         d.rng[g].pos = rng.pos;
         if (err) { atomicAdd(&d.counters[CNT_ERRORS], 1); c->searching = 0; c->active = 0; }
         if (FORCED && f_sel) { atomicAdd(&fstat[0], (unsigned long long)f_sel); if (f_hit) atomicAdd(&fstat[1], (unsigned long long)f_hit); }
+        if (GUMBEL && f_sel) { atomicAdd(&gd.stat[0], (unsigned long long)f_sel); if (f_hit) atomicAdd(&gd.stat[1], (unsigned long long)f_hit); }
     }
 }
 
@@ -493,12 +578,16 @@ __device__ __forceinline__ void collect_body(const EngineDev d, const double fk,
 // (at 138 VGPRs only 12 fit and the kernel ran in two rounds).
 template <int S>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S == 9 ? 4 : 1))) void k_collect(EngineDev d) {
-    collect_body<S, false>(d, 0.0, nullptr, nullptr);
+    collect_body<S, COLLECT_PLAIN>(d, 0.0, nullptr, nullptr, GumbelDev());
 }
 template <int S>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S == 9 ? 4 : 1))) void k_collect_forced(EngineDev d, double fk, const uint8_t* forced,
                                                                                                             unsigned long long* fstat) {
-    collect_body<S, true>(d, fk, forced, fstat);
+    collect_body<S, COLLECT_FORCED>(d, fk, forced, fstat, GumbelDev());
+}
+template <int S>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S == 9 ? 4 : 1))) void k_collect_gumbel(EngineDev d, GumbelDev gd) {
+    collect_body<S, COLLECT_GUMBEL>(d, 0.0, nullptr, nullptr, gd);
 }
 
 template <int S>
@@ -708,6 +797,77 @@ __global__ __launch_bounds__(64) void k_root_visits_pruned(EngineDev d, double f
     if (lane == 0 && pruned_game) pruned_game[g] = pg ? 1 : 0;
 }
 
+// The move of a Gumbel move whose search is over (gumbel.pick_move): argmax score(c) over the considered children
+// with the largest effort e(c) = c.n - n0[c] (pending counts as 0), ties to the lower action.  One wave, a lane per child, NPASS
+// passes; three wave reductions: the largest effort (64-bit keys as in pruned_counts), the largest score among its holders, the
+// lowest child index among the ties.  Returns the child index (wave-uniform), -1 when no child is considered.  The tree is only read.
+template <int S>
+__device__ __forceinline__ int gumbel_pick(const NodeRec* arena, const SearchCfg& sc, int blk, int nchild, const double* gl, const int32_t* n0,
+                                           double c_visit, double c_scale) {
+    constexpr int HS = TreeGeo<S>::HS, NPASS = TreeGeo<S>::NPASS;
+    const int lane = lane_id();
+    NodeRec ch[NPASS];
+    double glv[NPASS];
+    int ev[NPASS];
+    int maxn = 0;
+    unsigned long long key = 0;                                        // 0 = no considered child seen
+#pragma unroll
+    for (int j = 0; j < NPASS; ++j) {
+        const int i = j * 64 + lane;
+        glv[j] = -INFINITY; ev[j] = 0;
+        ch[j].prior = 0.0; ch[j].w = 0.f; ch[j].var = 0.f; ch[j].n = 0; ch[j].pending = 0; ch[j].block = -1; ch[j].action = 0; ch[j].flags = 0; ch[j].term = 0;
+        if (i < nchild) {
+            ch[j] = arena[blk + HS + i];
+            glv[j] = gl[i];
+            ev[j] = ch[j].n - n0[i]; ev[j] = ev[j] < 0 ? 0 : ev[j];
+            maxn = ch[j].n > maxn ? ch[j].n : maxn;
+            if (glv[j] > -INFINITY) { const unsigned long long k = ((unsigned long long)(uint32_t)ev[j] << 32) | 1u; key = k > key ? k : key; }
+        }
+    }
+    key = wave_max_u64(key);
+    if (key == 0) return -1;
+    const int top = (int)(uint32_t)(key >> 32);
+    maxn = wave_max_i32(maxn);
+    const double mult = (c_visit + (double)maxn) * c_scale;
+    double scv[NPASS], best = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < NPASS; ++j) {
+        scv[j] = -INFINITY;
+        if (glv[j] > -INFINITY && ev[j] == top) scv[j] = gumbel_score(glv[j], mult, ch[j]);
+        best = scv[j] > best ? scv[j] : best;
+    }
+    best = wave_max(best);
+    unsigned long long low = 0;                                        // ~index of the lowest tied child, as a maximum
+#pragma unroll
+    for (int j = 0; j < NPASS; ++j) {
+        const int i = j * 64 + lane;
+        if (glv[j] > -INFINITY && ev[j] == top && scv[j] == best) { const unsigned long long k = (uint32_t)~(uint32_t)i; low = k > low ? k : low; }
+    }
+    low = wave_max_u64(low);
+    return low ? (int)~(uint32_t)low : -1;
+}
+
+// tg_sp_gumbel_move: the move of every game inside a Gumbel move (-1, gumbel_game 0 for the others and for a game whose status is
+// not TG_ROOT_OK).  A read-out: every reference is checked.
+template <int S>
+__global__ __launch_bounds__(64) void k_gumbel_move(EngineDev d, GumbelDev gd, int32_t* action, uint8_t* gumbel_game) {
+    const int g = blockIdx.x, lane = lane_id();
+    NodeRec rec; rec.n = 0; rec.pending = 0; rec.w = 0.f; rec.var = 0.f; rec.flags = 0;
+    int blk;
+    const int st = root_status<S>(d, g, rec, blk);
+    int a = -1;
+    bool gg = false;
+    if (st == TG_ROOT_OK) {
+        const int nchild = checked_nchild<S>(d.arena, d.sc, blk);
+        if (nchild >= 0 && __builtin_amdgcn_readfirstlane((int)gd.flag[g]) != 0) {
+            gg = true;
+            const int idx = gumbel_pick<S>(d.arena, d.sc, blk, nchild, gd.gl + (size_t)g * d.sc.A, gd.n0 + (size_t)g * d.sc.A, gd.c_visit, gd.c_scale);
+            if (idx >= 0 && idx < nchild) a = d.arena[blk + TreeGeo<S>::HS + idx].action;
+        }
+    }
+    if (lane == 0) { if (action) action[g] = a; if (gumbel_game) gumbel_game[g] = gg ? 1 : 0; }
+}
+
 // Dense per-action tables of the root's children + the root's own record (tg_sp_root_children).  Lanes go over the children in
 // passes of 64: the reads are the contiguous nchild*32 B run of the root's block; every output pointer may be null.
 template <int S>
@@ -837,9 +997,13 @@ __global__ __launch_bounds__(64) void k_tree_pv(EngineDev d, int D, int32_t* o_a
 // finishes, rec_out = the number of its plies without the mark (the positions k_harvest will write).
 // FORCED (forced playouts; launched only while k > 0): the counts a forced game records are the pruned ones, and the
 // game's forced flag ends with the move.  The tree that is re-rooted keeps n, w and var as searched.
-template <int S, bool FORCED>
+// GUMBEL (Gumbel root search; launched only while m > 0): `forced` is the Gumbel flag, which ends with the move in
+// the same way; a Gumbel game records the counts staged for it (gtarget, by action; gstaged[g], cleared here), its raw visits
+// when nothing was staged.
+template <int S, int MODE>
 __device__ __forceinline__ void play_body(const EngineDev& d, const int32_t* actions, uint8_t* done_out, int32_t* moves_out, int32_t* rec_out,
-                                          const double fk, uint8_t* forced) {
+                                          const double fk, uint8_t* forced, const int32_t* gtarget, uint8_t* gstaged) {
+    constexpr bool FORCED = MODE == COLLECT_FORCED, GUMBEL = MODE == COLLECT_GUMBEL;
     using G = Geo<S>;
     constexpr int HS = TreeGeo<S>::HS, NPASS = TreeGeo<S>::NPASS;
     __shared__ WaveLds<S> lds;
@@ -850,8 +1014,11 @@ __device__ __forceinline__ void play_body(const EngineDev& d, const int32_t* act
     GameCtl* c = &d.ctl[g];
     const uint8_t skip = d.ply_skip[g];
     // the forced flag ends with this call whichever way the kernel leaves: read once, cleared before the first exit
-    const bool fgame = FORCED && __builtin_amdgcn_readfirstlane((int)forced[g]) != 0;
-    if (FORCED && lane == 0) forced[g] = 0;
+    const bool fgame = (FORCED || GUMBEL) && __builtin_amdgcn_readfirstlane((int)forced[g]) != 0;
+    bool staged = false;
+    if constexpr (GUMBEL) staged = fgame && __builtin_amdgcn_readfirstlane((int)gstaged[g]) != 0;
+    if ((FORCED || GUMBEL) && lane == 0) forced[g] = 0;
+    if (GUMBEL && lane == 0) gstaged[g] = 0;
     if (lane == 0) { d.game_nslot[g] = 0; rec_out[g] = 0; }
     if (c->finished || c->error) { if (lane == 0) { done_out[g] = c->error ? 2 : 1; moves_out[g] = c->moves; } return; }
     const SearchCfg& sc = d.sc;
@@ -883,6 +1050,8 @@ __device__ __forceinline__ void play_body(const EngineDev& d, const int32_t* act
 #pragma unroll
             for (int j = 0; j < NPASS; ++j)
                 if (pa[j] >= 0) cnt[pa[j]] = pn[j];
+        } else if (GUMBEL && staged) {
+            for (int a2 = lane; a2 < G::A; a2 += 64) cnt[a2] = gtarget[(size_t)g * G::A + a2];
         } else {
             for (int i = lane; i < nchild; i += 64) { NodeRec r = old[rblk + HS + i]; cnt[r.action] = r.n; }
         }
@@ -1023,12 +1192,17 @@ __device__ __forceinline__ void play_body(const EngineDev& d, const int32_t* act
 
 template <int S>
 __global__ __launch_bounds__(64) void k_play(EngineDev d, const int32_t* actions, uint8_t* done_out, int32_t* moves_out, int32_t* rec_out) {
-    play_body<S, false>(d, actions, done_out, moves_out, rec_out, 0.0, nullptr);
+    play_body<S, COLLECT_PLAIN>(d, actions, done_out, moves_out, rec_out, 0.0, nullptr, nullptr, nullptr);
 }
 template <int S>
 __global__ __launch_bounds__(64) void k_play_forced(EngineDev d, const int32_t* actions, uint8_t* done_out, int32_t* moves_out, int32_t* rec_out,
                                                     double fk, uint8_t* forced) {
-    play_body<S, true>(d, actions, done_out, moves_out, rec_out, fk, forced);
+    play_body<S, COLLECT_FORCED>(d, actions, done_out, moves_out, rec_out, fk, forced, nullptr, nullptr);
+}
+template <int S>
+__global__ __launch_bounds__(64) void k_play_gumbel(EngineDev d, const int32_t* actions, uint8_t* done_out, int32_t* moves_out, int32_t* rec_out,
+                                                    uint8_t* gflag, const int32_t* gtarget, uint8_t* gstaged) {
+    play_body<S, COLLECT_GUMBEL>(d, actions, done_out, moves_out, rec_out, 0.0, gflag, gtarget, gstaged);
 }
 
 // Finished games -> training positions, on the device (self_play.py:929-967 minus the 8-fold augmentation, which the replay
@@ -1220,6 +1394,14 @@ template <class F> void parallel_games(int n, F f) {
     for (auto& x : th) x.join();
 }
 
+// the kernel-argument view of the Gumbel state
+GumbelDev gumbel_dev(const Engine* e) {
+    GumbelDev gd;
+    gd.gl = e->d_noise; gd.n0 = e->d_gumbel_n0; gd.N0 = e->d_gumbel_N0; gd.flag = e->d_gumbel; gd.stat = e->d_gumbel_stat;
+    gd.c_visit = e->gumbel_c_visit; gd.c_scale = e->gumbel_c_scale; gd.m = e->gumbel_m;
+    return gd;
+}
+
 // The get_action_probs prologue (self_play.py:659-663) behind both entry points.  noise_g == nullptr: every game is noised when
 // noise_all, none otherwise; sims_g == nullptr: every game's budget is `sims`; record_g == nullptr: every game records its ply.
 int begin_move(tg_ctx* ctx, const char* who, bool noise_all, const uint8_t* noise_g, int sims, const int32_t* sims_g, const uint8_t* record_g) {
@@ -1249,7 +1431,35 @@ int begin_move(tg_ctx* ctx, const char* who, bool noise_all, const uint8_t* nois
         TG_HIP(ctx, hipMemcpyAsync(e->d_i32 + G, e->h_sims.data(), sizeof(int32_t) * G, hipMemcpyHostToDevice, ctx->stream));
         d_sims = e->d_i32 + G;
     }
-    if (noise_all) {                                                   // root.dirichlet_prior(), self_play.py:659-660
+    const bool gumbel = noise_all && e->gumbel_m > 0;                  // Gumbel moves get no Dirichlet noise
+    if (gumbel) {
+        // priors and child counts of the roots -> host; per Gumbel game nchild draws from its own stream, gl = g + log(prior), the
+        // m_eff largest kept (ties: the lower action), the others -inf; the table goes back through d_noise, idle in such a move
+        int32_t* d_nchild = e->d_i32;
+        TG_LAUNCH(ctx, k_root_priors, G, e->dev, e->d_noise, d_nchild);
+        TG_HIP(ctx, hipMemcpyAsync(e->h_nchild.data(), d_nchild, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
+        TG_HIP(ctx, hipMemcpyAsync(e->h_noise.data(), e->d_noise, sizeof(double) * (size_t)G * A, hipMemcpyDeviceToHost, ctx->stream));
+        TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        { int rc = rng_to_host(ctx); if (rc) return rc; }
+        const int m = e->gumbel_m;
+        parallel_games(G, [&](int g) {
+            const int n = e->h_nchild[g] < A ? e->h_nchild[g] : A;
+            if (n <= 0 || (noise_g && !noise_g[g])) return;
+            double* gv = &e->h_gumbel[(size_t)g * A];
+            double* gl = &e->h_noise[(size_t)g * A];                   // in: the priors, out: the table
+            tg_host_mt_gumbel(&e->h_rng[g], n, gv);
+            for (int i = 0; i < n; ++i) gl[i] = gv[i] + (gl[i] > 0.0 ? log(gl[i]) : -INFINITY);
+            const int m_eff = m < n ? m : n;
+            if (m_eff < n) {                                           // gv: scratch for the order
+                std::vector<int> ord(n);
+                for (int i = 0; i < n; ++i) ord[i] = i;
+                std::partial_sort(ord.begin(), ord.begin() + m_eff, ord.end(),
+                                  [&](int a, int b) { return gl[a] > gl[b] || (gl[a] == gl[b] && a < b); });
+                for (int i = m_eff; i < n; ++i) gl[ord[i]] = -INFINITY;
+            }
+        });
+        TG_HIP(ctx, hipMemcpyAsync(e->d_noise, e->h_noise.data(), sizeof(double) * (size_t)G * A, hipMemcpyHostToDevice, ctx->stream));
+    } else if (noise_all) {                                            // root.dirichlet_prior(), self_play.py:659-660
         int32_t* d_nchild = e->d_i32;
         TG_LAUNCH(ctx, k_root_info, G, e->dev, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr,
                   d_nchild, (float*)nullptr);
@@ -1265,6 +1475,7 @@ int begin_move(tg_ctx* ctx, const char* who, bool noise_all, const uint8_t* nois
     }
     { int rc = rng_to_device(ctx); if (rc) return rc; }
     TG_LAUNCH(ctx, k_begin, G, e->dev, sims, d_sims, d_skip, e->d_forced, d_noise_g, (noise_all && e->forced_k > 0.0) ? 1 : 0);
+    if (gumbel) TG_LAUNCH(ctx, k_begin_gumbel, G, e->dev, e->d_gumbel, d_noise_g, e->d_gumbel_n0, e->d_gumbel_N0, e->d_gumbel_staged);
     TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return TG_OK;
 }
@@ -1365,6 +1576,10 @@ int tg_engine_create(tg_ctx* ctx) {
     TG_HIP(ctx, hipMemsetAsync(e->d_forced, 0, (size_t)G, ctx->stream));
     TG_HIP(ctx, hipMalloc((void**)&e->d_forced_stat, sizeof(unsigned long long) * 2));
     TG_HIP(ctx, hipMemsetAsync(e->d_forced_stat, 0, sizeof(unsigned long long) * 2, ctx->stream));
+    TG_HIP(ctx, hipMalloc((void**)&e->d_gumbel, (size_t)G));
+    TG_HIP(ctx, hipMemsetAsync(e->d_gumbel, 0, (size_t)G, ctx->stream));
+    TG_HIP(ctx, hipMalloc((void**)&e->d_gumbel_stat, sizeof(unsigned long long) * 2));
+    TG_HIP(ctx, hipMemsetAsync(e->d_gumbel_stat, 0, sizeof(unsigned long long) * 2, ctx->stream));
     e->h_noise.resize((size_t)G * A);
     e->h_nchild.resize(G);
     e->arena_bytes = arena_bytes;
@@ -1393,7 +1608,8 @@ void tg_engine_destroy(tg_ctx* ctx) {
     if (!e) return;
     void* ptrs[] = {e->dev.arena, e->dev.ring, e->dev.pool, e->dev.chunk_ids, e->dev.ctl, e->dev.rng, e->dev.path_nodes, e->dev.path_len, e->dev.path_row, e->dev.row_slot,
                     e->dev.obs_bits, e->dev.game_nslot, e->dev.game_off, e->dev.game_act, e->dev.policy, e->dev.value, e->dev.counters, e->d_noise, e->d_i32, e->d_f32, e->d_u8,
-                    e->d_fin, e->dev.hist_obs, e->dev.hist_cnt, e->dev.hist_pl, e->dev.ply_skip, e->d_forced, e->d_forced_stat};
+                    e->d_fin, e->dev.hist_obs, e->dev.hist_cnt, e->dev.hist_pl, e->dev.ply_skip, e->d_forced, e->d_forced_stat,
+                    e->d_gumbel, e->d_gumbel_stat, e->d_gumbel_n0, e->d_gumbel_N0, e->d_gumbel_target, e->d_gumbel_staged};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->h_rng) (void)hipHostFree(e->h_rng);
     e->obs_f32.release(); e->readout.release(); e->snap_tab.release(); e->snap_stage.release(); e->hv_obs.release(); e->hv_cnt.release(); e->hv_z.release(); e->hv_own.release(); e->hv_pl.release(); e->hv_game.release();
@@ -1431,6 +1647,10 @@ int tg_sp_reset(tg_ctx* ctx, const uint32_t* seeds, const uint8_t* mask) {
     // no restarted slot is inside a forced move (forced playouts); the flags of the other slots stay
     if (!mask) { TG_HIP(ctx, hipMemsetAsync(e->d_forced, 0, (size_t)G, ctx->stream)); }
     else hipLaunchKernelGGL(k_clear_forced, dim3((G + 255) / 256), dim3(256), 0, ctx->stream, e->d_forced, (const uint8_t*)d_mask, G);
+    if (e->gumbel_m > 0) {                                            // ... nor inside a Gumbel move (the flags are all 0 while m = 0)
+        if (!mask) { TG_HIP(ctx, hipMemsetAsync(e->d_gumbel, 0, (size_t)G, ctx->stream)); }
+        else hipLaunchKernelGGL(k_clear_forced, dim3((G + 255) / 256), dim3(256), 0, ctx->stream, e->d_gumbel, (const uint8_t*)d_mask, G);
+    }
     if (!mask) hipLaunchKernelGGL(k_pool_init, dim3(64), dim3(256), 0, ctx->stream, e->dev, 0);
     else {
         hipLaunchKernelGGL(k_release, dim3(G), dim3(64), 0, ctx->stream, e->dev, (const uint8_t*)d_mask);
@@ -1464,6 +1684,7 @@ int tg_sp_reset_from(tg_ctx* ctx, const void* states, const uint8_t* mask) {
     e->fin_slot.clear(); e->fin_off.clear(); e->fin_positions = 0;
     TG_HIP(ctx, hipMemsetAsync(e->dev.ply_skip, 0, (size_t)G, ctx->stream));
     TG_HIP(ctx, hipMemsetAsync(e->d_forced, 0, (size_t)G, ctx->stream));          // (every slot is restarted or parked)
+    if (e->gumbel_m > 0) TG_HIP(ctx, hipMemsetAsync(e->d_gumbel, 0, (size_t)G, ctx->stream));
     // (unmasked slots are parked by k_reset and keep the one chunk they own until their next reset)
     hipLaunchKernelGGL(k_release, dim3(G), dim3(64), 0, ctx->stream, e->dev, (const uint8_t*)d_mask);
     hipLaunchKernelGGL(k_pool_publish, dim3(1), dim3(1), 0, ctx->stream, e->dev);
@@ -1574,6 +1795,7 @@ int tg_sp_collect(tg_ctx* ctx, int32_t* n_active, int32_t* n_rows) {
     const bool timed = e->tprof && e->tev_used + 4 <= e->tev.size();
     if (timed) { TG_HIP(ctx, hipEventRecord(e->tev[e->tev_used], ctx->stream)); }
     if (e->forced_k > 0.0) TG_LAUNCH(ctx, k_collect_forced, e->G, e->dev, e->forced_k, (const uint8_t*)e->d_forced, e->d_forced_stat);
+    else if (e->gumbel_m > 0) TG_LAUNCH(ctx, k_collect_gumbel, e->G, e->dev, gumbel_dev(e));
     else TG_LAUNCH(ctx, k_collect, e->G, e->dev);
     hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, ctx->stream, e->dev, e->R, 1);
     TG_HIP(ctx, hipGetLastError());
@@ -1710,6 +1932,8 @@ int tg_sp_forced_playouts(tg_ctx* ctx, double k) {
     if (!ctx) return TG_ERR_ARG;
     if (!ctx->eng || ctx->eng->G <= 0) TG_FAIL(ctx, TG_ERR_ARG, "tg_sp_forced_playouts: the context has no self-play engine (n_games = 0)");
     if (!std::isfinite(k) || k < 0.0) TG_FAIL(ctx, TG_ERR_ARG, "tg_sp_forced_playouts: k must be a finite number >= 0 (0 = off)");
+    if (k > 0.0 && ctx->eng->gumbel_m > 0)
+        TG_FAIL(ctx, TG_ERR_ARG, "tg_sp_forced_playouts: Gumbel root search is on (tg_sp_gumbel m > 0); both are rules for the same root");
     if (ctx->eng->batch_kind == BATCH_LEAVES) TG_FAIL(ctx, TG_ERR_STATE, "tg_sp_forced_playouts: an evaluation batch is pending");
     ctx->eng->forced_k = k;
     return TG_OK;
@@ -1742,6 +1966,97 @@ int tg_sp_forced_playouts_stats(tg_ctx* ctx, uint64_t* root_selections, uint64_t
     TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (root_selections) *root_selections = h[0];
     if (forced_selections) *forced_selections = h[1];
+    return TG_OK;
+}
+
+// ---- Gumbel root search -----------------------------------------------------------------------------------------
+int tg_sp_gumbel(tg_ctx* ctx, int m, double c_visit, double c_scale) {
+    if (!ctx) return TG_ERR_ARG;
+    if (!ctx->eng || ctx->eng->G <= 0) TG_FAIL(ctx, TG_ERR_ARG, "tg_sp_gumbel: the context has no self-play engine (n_games = 0)");
+    Engine* e = ctx->eng;
+    if (m < 0) TG_FAIL(ctx, TG_ERR_ARG, "tg_sp_gumbel: m must be >= 0 (0 = off)");
+    if (!std::isfinite(c_visit) || !std::isfinite(c_scale)) TG_FAIL(ctx, TG_ERR_ARG, "tg_sp_gumbel: c_visit and c_scale must be finite numbers");
+    if (m > 0 && e->forced_k > 0.0)
+        TG_FAIL(ctx, TG_ERR_ARG, "tg_sp_gumbel: forced playouts are on (tg_sp_forced_playouts k > 0); both are rules for the same root");
+    if (e->batch_kind == BATCH_LEAVES) TG_FAIL(ctx, TG_ERR_STATE, "tg_sp_gumbel: an evaluation batch is pending");
+    TG_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    const size_t G = (size_t)e->G, GA = G * ctx->A;
+    if (m > 0 && !e->d_gumbel_n0) {                                   // the tables of a move, on first use
+        TG_HIP(ctx, hipMalloc((void**)&e->d_gumbel_n0, sizeof(int32_t) * GA));
+        TG_HIP(ctx, hipMalloc((void**)&e->d_gumbel_N0, sizeof(int32_t) * G));
+        TG_HIP(ctx, hipMalloc((void**)&e->d_gumbel_target, sizeof(int32_t) * GA));
+        TG_HIP(ctx, hipMalloc((void**)&e->d_gumbel_staged, G));
+        TG_HIP(ctx, hipMemsetAsync(e->d_gumbel_n0, 0, sizeof(int32_t) * GA, ctx->stream));
+        TG_HIP(ctx, hipMemsetAsync(e->d_gumbel_N0, 0, sizeof(int32_t) * G, ctx->stream));
+        TG_HIP(ctx, hipMemsetAsync(e->d_gumbel_target, 0, sizeof(int32_t) * GA, ctx->stream));
+        TG_HIP(ctx, hipMemsetAsync(e->d_gumbel_staged, 0, G, ctx->stream));
+        e->h_gumbel.assign(GA, 0.0);
+    }
+    if (m == 0 && e->gumbel_m > 0) {                                  // switched off: no game is inside a Gumbel move any more
+        TG_HIP(ctx, hipMemsetAsync(e->d_gumbel, 0, G, ctx->stream));
+        TG_HIP(ctx, hipMemsetAsync(e->d_gumbel_staged, 0, G, ctx->stream));
+    }
+    TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    e->gumbel_m = m; e->gumbel_c_visit = c_visit; e->gumbel_c_scale = c_scale;
+    return TG_OK;
+}
+
+int tg_sp_gumbel_get(tg_ctx* ctx, int* m, double* c_visit, double* c_scale) {
+    if (!ctx || !ctx->eng) return TG_ERR_ARG;
+    if (m) *m = ctx->eng->gumbel_m;
+    if (c_visit) *c_visit = ctx->eng->gumbel_c_visit;
+    if (c_scale) *c_scale = ctx->eng->gumbel_c_scale;
+    return TG_OK;
+}
+
+int tg_sp_gumbel_move(tg_ctx* ctx, int32_t* action, uint8_t* gumbel_game) {
+    NEED_READOUT(ctx, "tg_sp_gumbel_move");
+    Engine* e = ctx->eng;
+    const size_t G = (size_t)e->G;
+    if (e->gumbel_m <= 0) {                                           // off: no game is in a Gumbel move, and nothing is launched
+        for (size_t g = 0; g < G; ++g) { if (action) action[g] = -1; if (gumbel_game) gumbel_game[g] = 0; }
+        return TG_OK;
+    }
+    // staging: action i32[G] | gumbel_game u8[G]
+    if (e->readout.reserve(G * 5)) TG_FAIL(ctx, TG_ERR_HIP, "hipMalloc failed");
+    int32_t* d_a = (int32_t*)e->readout.p; uint8_t* d_gg = (uint8_t*)(d_a + G);
+    TG_LAUNCH(ctx, k_gumbel_move, e->G, e->dev, gumbel_dev(e), d_a, d_gg);
+    if (action) TG_HIP(ctx, hipMemcpyAsync(action, d_a, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
+    if (gumbel_game) TG_HIP(ctx, hipMemcpyAsync(gumbel_game, d_gg, G, hipMemcpyDeviceToHost, ctx->stream));
+    TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return TG_OK;
+}
+
+int tg_sp_gumbel_table(tg_ctx* ctx, double* gl) {
+    NEED_READOUT(ctx, "tg_sp_gumbel_table");
+    Engine* e = ctx->eng;
+    if (!gl) return TG_ERR_ARG;
+    if (e->gumbel_m <= 0) TG_FAIL(ctx, TG_ERR_STATE, "tg_sp_gumbel_table: Gumbel root search is off (tg_sp_gumbel m = 0)");
+    TG_HIP(ctx, hipMemcpyAsync(gl, e->d_noise, sizeof(double) * (size_t)e->G * ctx->A, hipMemcpyDeviceToHost, ctx->stream));
+    TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return TG_OK;
+}
+
+int tg_sp_gumbel_target(tg_ctx* ctx, const int32_t* counts, const uint8_t* mask) {
+    NEED_READOUT(ctx, "tg_sp_gumbel_target");
+    Engine* e = ctx->eng;
+    if (!counts) return TG_ERR_ARG;
+    if (e->gumbel_m <= 0) TG_FAIL(ctx, TG_ERR_STATE, "tg_sp_gumbel_target: Gumbel root search is off (tg_sp_gumbel m = 0)");
+    const size_t G = (size_t)e->G;
+    TG_HIP(ctx, hipMemcpyAsync(e->d_gumbel_target, counts, sizeof(int32_t) * G * ctx->A, hipMemcpyHostToDevice, ctx->stream));
+    if (mask) TG_HIP(ctx, hipMemcpyAsync(e->d_gumbel_staged, mask, G, hipMemcpyHostToDevice, ctx->stream));
+    else TG_HIP(ctx, hipMemsetAsync(e->d_gumbel_staged, 1, G, ctx->stream));
+    TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return TG_OK;
+}
+
+int tg_sp_gumbel_stats(tg_ctx* ctx, uint64_t* root_selections, uint64_t* fallback_selections) {
+    NEED_ENGINE(ctx);
+    unsigned long long h[2] = {0, 0};
+    TG_HIP(ctx, hipMemcpyAsync(h, ctx->eng->d_gumbel_stat, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (root_selections) *root_selections = h[0];
+    if (fallback_selections) *fallback_selections = h[1];
     return TG_OK;
 }
 
@@ -1794,6 +2109,8 @@ int tg_sp_play(tg_ctx* ctx, const int32_t* actions, uint8_t* done) {
     std::vector<int32_t> prev = e->h_moves;
     e->h_rec.resize(G);
     if (e->forced_k > 0.0) TG_LAUNCH(ctx, k_play_forced, G, e->dev, (const int32_t*)d_act, e->d_u8, d_moves, d_rec, e->forced_k, e->d_forced);
+    else if (e->gumbel_m > 0) TG_LAUNCH(ctx, k_play_gumbel, G, e->dev, (const int32_t*)d_act, e->d_u8, d_moves, d_rec, e->d_gumbel,
+                                        (const int32_t*)e->d_gumbel_target, e->d_gumbel_staged);
     else TG_LAUNCH(ctx, k_play, G, e->dev, (const int32_t*)d_act, e->d_u8, d_moves, d_rec);
     hipLaunchKernelGGL(k_pool_publish, dim3(1), dim3(1), 0, ctx->stream, e->dev);      // the old trees' chunks are poppable from here on
     hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, ctx->stream, e->dev, e->R, 0);

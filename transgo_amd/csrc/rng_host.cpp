@@ -106,6 +106,12 @@ int tg_host_mt_dirichlet(tg_mt19937* s, double alpha, int32_t n, double* out) {
     return 0;
 }
 
+// n Gumbel(0, 1) variates (Gumbel root search): one random_sample() u each, g = -log(-log(u)) with libm's log;
+// u == 0 gives -inf (log(0) = -inf, log(+inf) = +inf).
+void tg_host_mt_gumbel(tg_mt19937* s, int32_t n, double* out) {
+    for (int i = 0; i < n; i++) out[i] = -log(-log(next_double(s)));
+}
+
 // Playout cap randomization: the draw that makes ply `ply` of the game seeded `seed` a full or a fast search.
 // Counter-based (the splitmix64 finaliser, twice), so it needs no state and leaves the game's MT19937 stream alone.
 static inline uint64_t cap_mix(uint64_t x) {

@@ -104,6 +104,16 @@ __device__ __forceinline__ double wave_max(double v) {
     for (int off = 32; off; off >>= 1) { double o = __shfl_xor(v, off); v = o > v ? o : v; }
     return v;
 }
+__device__ __forceinline__ int wave_max_i32(int v) {
+#pragma unroll
+    for (int off = 32; off; off >>= 1) { const int o = __shfl_xor(v, off); v = o > v ? o : v; }
+    return v;
+}
+__device__ __forceinline__ int wave_min_i32(int v) {
+#pragma unroll
+    for (int off = 32; off; off >>= 1) { const int o = __shfl_xor(v, off); v = o < v ? o : v; }
+    return v;
+}
 __device__ __forceinline__ int nth_set_bit(uint64_t m, int k) {      // k-th (0-based) set bit of m
     for (int i = 0; i < k; ++i) m &= m - 1;
     return __ffsll((long long)m) - 1;
@@ -167,6 +177,38 @@ __device__ __forceinline__ double puct_score(const NodeRec& c, double sqrt_paren
     }
     const float q = -(c.w / (float)(c.n + 1));
     return u + s + (double)q;
+}
+
+// ---- Gumbel root search (transgo_amd/gumbel.py is the definition) -------------------------------------------------
+// What the selection kernel of a Gumbel move carries besides the engine: the gl table and the base counts by child index, the
+// per-game flags, the parameters and two counters.  Dead in every other instantiation.
+struct GumbelDev {
+    const double* gl = nullptr;      // [G][A]  g + log(prior) of the considered children, -inf for the others
+    const int32_t* n0 = nullptr;     // [G][A]  c.n at the start of the move
+    const int32_t* N0 = nullptr;     // [G]     root.n at the start of the move
+    const uint8_t* flag = nullptr;   // [G]     the move in progress is a Gumbel move
+    unsigned long long* stat = nullptr;   // [2] root selections, fallback selections
+    double c_visit = 0.0, c_scale = 0.0;
+    int m = 0;
+};
+// v(t) of gumbel.considered_visit: the sequential-halving schedule in closed form, wave-uniform integers only.
+__device__ __forceinline__ int considered_visit(int m_eff, int n, int t) {
+    if (m_eff <= 1) return t;
+    int s = t < n - 1 ? t : n - 1;
+    s = s < 0 ? 0 : s;
+    const int L = 32 - __clz(m_eff - 1);                              // ceil(log2(m_eff)), m_eff >= 2
+    int k = m_eff, base = 0;
+    for (;;) {                                                         // every phase takes at least 2 steps off s
+        int x = n / (L * k); x = x < 1 ? 1 : x;
+        if (s < x * k) return base + s / k;
+        s -= x * k; base += x;
+        k = k / 2 < 2 ? 2 : k / 2;
+    }
+}
+__device__ __forceinline__ int gumbel_effort(const NodeRec& c, int n0, int wu) { return (c.n - n0) + (wu > 0 ? c.pending / wu : 0); }
+__device__ __forceinline__ double gumbel_score(double gl, double mult, const NodeRec& c) {     // mult = (c_visit + maxN) * c_scale
+    const float q = -(c.w / (float)(c.n + 1));
+    return gl + mult * (double)q;
 }
 
 // backpropagate + value_mean_var for the node at path position d of `len` (self_play.py:758-764, :84-88): nodes of a

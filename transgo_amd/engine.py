@@ -113,7 +113,8 @@ class SelfPlayEngine:
     def __init__(self, n_games, board_size=9, num_simulation=210, parallel_readouts=4, c_puct1=3, c_puct2=0.05,
                  wu_loss=2, komi=7.5, max_step=120, encode_dim=10, net_blocks=6, net_filters=128, arena_slots=0,
                  device=0, evaluator=None, net_precision="f32", record_games=True, pool_slots=0, eval_symmetry="none",
-                 symmetry_seed=0, eval_cache_entries=0, forced_playouts_k=0.0):
+                 symmetry_seed=0, eval_cache_entries=0, forced_playouts_k=0.0, gumbel_m=0, gumbel_c_visit=50.0,
+                 gumbel_c_scale=1.0):
         cfg = _lib.default_config()
         cfg.record_games = 1 if record_games else 0       # per-move records in HBM for tg_sp_harvest (self-play); evaluation matches need none
         cfg.net_precision = {"f32": 0, "f16": 1, "f16r": 2, "f32x3": 3}[net_precision]
@@ -139,6 +140,9 @@ class SelfPlayEngine:
         self.forced_playouts_k = 0.0
         if forced_playouts_k:
             self.set_forced_playouts(forced_playouts_k)
+        self.gumbel_m, self.gumbel_c_visit, self.gumbel_c_scale = 0, 50.0, 1.0
+        if gumbel_m:
+            self.set_gumbel(gumbel_m, gumbel_c_visit, gumbel_c_scale)
 
     def close(self):
         self.ctx.close()
@@ -200,6 +204,72 @@ class SelfPlayEngine:
         a, b = ctypes.c_uint64(), ctypes.c_uint64()
         self.ctx.call("tg_sp_forced_playouts_stats", ctypes.byref(a), ctypes.byref(b))
         return dict(root_selections=int(a.value), forced_selections=int(b.value))
+
+    # ---- Gumbel root search (tg_sp_gumbel) --------------------------------------------------------------------
+    def set_gumbel(self, m, c_visit=50.0, c_scale=1.0):
+        """m > 0: a search that would begin with root noise is a Gumbel move instead -- no Dirichlet noise, m root actions sampled
+        with the Gumbel-top-k trick, the budget spent on them by sequential halving (transgo_amd.gumbel holds the definition).
+        0 = off.  Context state: a restored snapshot does not carry it.  Refused together with forced playouts."""
+        from . import gumbel as _gb
+        m, c_visit, c_scale = _gb.check_params(m, c_visit, c_scale)
+        self.ctx.call("tg_sp_gumbel", m, ctypes.c_double(c_visit), ctypes.c_double(c_scale))
+        self.gumbel_m, self.gumbel_c_visit, self.gumbel_c_scale = m, c_visit, c_scale
+
+    def get_gumbel(self):
+        m, cv, cs = ctypes.c_int(), ctypes.c_double(), ctypes.c_double()
+        self.ctx.call("tg_sp_gumbel_get", ctypes.byref(m), ctypes.byref(cv), ctypes.byref(cs))
+        return int(m.value), float(cv.value), float(cs.value)
+
+    def gumbel_moves(self):
+        """(actions int32[G], gumbel_game bool[G]): the deterministic move of every game inside a Gumbel move whose search is over
+        (-1 / False for every other game)."""
+        act = np.full(self.G, -1, np.int32); gg = np.zeros(self.G, np.uint8)
+        self.ctx.call("tg_sp_gumbel_move", _ptr(act), _ptr(gg))
+        return act, gg != 0
+
+    def gumbel_table(self):
+        """The gl table of the Gumbel moves in progress as the engine uses it, by action: float64 [G, A], -inf for a child that is
+        not considered and for an action that is not legal; rows of games that are not in a Gumbel move are all -inf."""
+        raw = np.zeros((self.G, self.A), np.float64)
+        self.ctx.call("tg_sp_gumbel_table", _ptr(raw))
+        legal = (self.root_children()["flags"] & self.CHILD_PRESENT) != 0
+        gg = self.gumbel_moves()[1]
+        out = np.full((self.G, self.A), -np.inf)
+        for g in np.flatnonzero(gg):
+            acts = np.flatnonzero(legal[g])
+            out[g, acts] = raw[g, :len(acts)]
+        return out
+
+    def gumbel_targets(self, games=None):
+        """(pi' float64 [G, A], counts int32 [G, A]) of the games in a Gumbel move (default: gumbel_moves()'s): the improved policy
+        (gumbel.improved_policy over root_children()) and its fixed-point form, 0 for the other games."""
+        from . import gumbel as _gb
+        if games is None:
+            games = self.gumbel_moves()[1]
+        pi = _gb.improved_policy(self.root_children(), self.gumbel_c_visit, self.gumbel_c_scale, games)
+        return pi, _gb.fixed_point(pi)
+
+    def stage_gumbel_targets(self, counts, games):
+        """tg_sp_gumbel_target: the counts play() records for `games` (bool[G]) in place of their visit counts."""
+        self.ctx.call("tg_sp_gumbel_target", _ptr(np.ascontiguousarray(counts, np.int32)), _ptr(np.ascontiguousarray(games, np.uint8)))
+
+    def gumbel_stats(self):
+        """Root selections made in Gumbel moves so far, and how many of them found no considered child at the schedule's value."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self.ctx.call("tg_sp_gumbel_stats", ctypes.byref(a), ctypes.byref(b))
+        return dict(root_selections=int(a.value), fallback_selections=int(b.value))
+
+    def choose_gumbel_moves(self, visits, steps, selfplay=True):
+        """Move selection while gumbel_m > 0: the games in a Gumbel move take gumbel_moves()'s action, their pi is the improved
+        policy, which is staged for play() to record, and their streams are not touched; every other game goes through
+        choose_moves.  Returns (actions, pis, gumbel_game)."""
+        gact, gg = self.gumbel_moves()
+        actions, pis = self.choose_moves(visits, steps, selfplay, skip=gg)
+        if gg.any():
+            pi, counts = self.gumbel_targets(gg)
+            self.stage_gumbel_targets(counts, gg)
+            actions[gg] = gact[gg]; pis[gg] = pi[gg]
+        return actions, pis, gg
 
     # ---- evaluation of the pending batch --------------------------------------------------------------------------------
     def _evaluate(self, rows=None):
@@ -347,14 +417,17 @@ class SelfPlayEngine:
         self.ctx.call("tg_sp_pv", depth, _ptr(act), _ptr(n), _ptr(w), _ptr(ln))
         return act, n, w, ln
 
-    def choose_moves(self, visits, steps, selfplay=True):
+    def choose_moves(self, visits, steps, selfplay=True, skip=None):
         """self_play.py:666-683 for every live game, in NumPy float64 with the reference's own operations:
         counts==1 -> 0, pi = counts/sum, p ~ counts**(1/tau), and np.random.choice(A, p) spelt out as NumPy implements it
         (mtrand.pyx: cdf = p.cumsum(); cdf /= cdf[-1]; cdf.searchsorted(random_sample(), 'right')) with the uniform
         drawn from the game's own stream.  Vectorised over games; every operation is element-wise or a last-axis
         reduction, so each row equals the per-game 1-D computation bit for bit (tests/test_host_logic.py checks it
-        against the literal per-game form, choose_moves_reference)."""
+        against the literal per-game form, choose_moves_reference).  skip bool[G]: games that choose otherwise (a Gumbel move):
+        no draw from their streams, action 0 and pi 0 here."""
         live = ~self.finished
+        if skip is not None:
+            live = live & ~np.asarray(skip, bool)
         u = np.zeros(self.G, np.float64)
         self.ctx.call("tg_sp_draw_uniform", _ptr(u), _ptr(live.astype(np.uint8)))
         return choose_moves_batch(visits, steps, u, live, selfplay)

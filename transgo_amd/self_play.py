@@ -99,7 +99,9 @@ class BatchedSelfPlay:
             net_precision=getattr(config, "inference_dtype", "f32"),
             eval_symmetry=getattr(config, "eval_symmetry", "none"), symmetry_seed=getattr(config, "symmetry_seed", 0),
             eval_cache_entries=getattr(config, "eval_cache_entries", 0) if eval_cache_entries is None else eval_cache_entries,
-            forced_playouts_k=getattr(config, "forced_playouts_k", 0.0))
+            forced_playouts_k=getattr(config, "forced_playouts_k", 0.0),
+            gumbel_m=getattr(config, "gumbel_m", 0), gumbel_c_visit=getattr(config, "gumbel_c_visit", 50.0),
+            gumbel_c_scale=getattr(config, "gumbel_c_scale", 1.0))
         self.seed_fn = seed_fn
         self.games_started = np.zeros(n_games, np.int64)
         self.seeds = np.zeros(n_games, np.uint32)          # seed of the game now running in each slot
@@ -204,7 +206,12 @@ class BatchedSelfPlay:
         # forced playouts: the games whose move was a noised one choose from their pruned counts (with the playout cap on these are
         # the full plies); every other game, and every game while k = 0, from the raw ones
         vis, steps = eng.root_visits(pruned=True) if eng.forced_playouts_k > 0.0 else eng.root_visits()
-        actions, _ = eng.choose_moves(vis, steps, selfplay)
+        if eng.gumbel_m > 0:
+            # Gumbel root search: the games whose move was a Gumbel move (with the playout cap on, the full plies) play the winner of
+            # the sequential halving and record the improved policy; every other game chooses from its counts as ever
+            actions, _, _ = eng.choose_gumbel_moves(vis, steps, selfplay)
+        else:
+            actions, _ = eng.choose_moves(vis, steps, selfplay)
         t2 = time.perf_counter()
         done = eng.play(actions)
         t3 = time.perf_counter()
@@ -257,6 +264,8 @@ class BatchedSelfPlay:
         self._check_part(state, snap)
         self.engine.restore(snap)                                      # refuses a mismatched geometry before it changes anything
         self.engine.set_forced_playouts(getattr(self.config, "forced_playouts_k", 0.0))      # context state, not part of a snapshot
+        self.engine.set_gumbel(getattr(self.config, "gumbel_m", 0), getattr(self.config, "gumbel_c_visit", 50.0),
+                               getattr(self.config, "gumbel_c_scale", 1.0))
         self.games_started = np.asarray(state["games_started"], np.int64)
         self.seeds = np.asarray(state["seeds"], np.uint32)
         self.moves_played, self.games_finished = int(state["moves_played"]), int(state["games_finished"])
@@ -487,7 +496,10 @@ class WP_MCTS:
         vis, _, _, steps, obs = self.engine.root_info()
         if self.engine.forced_playouts_k > 0.0:
             vis = self.engine.root_visits(pruned=True)[0]
-        actions, pis = self.engine.choose_moves(vis, steps, selfplay=bool(is_selfplay))
+        if self.engine.gumbel_m > 0:                   # a Gumbel move: the halving's winner and the improved policy pi'
+            actions, pis, _ = self.engine.choose_gumbel_moves(vis, steps, selfplay=bool(is_selfplay))
+        else:
+            actions, pis = self.engine.choose_moves(vis, steps, selfplay=bool(is_selfplay))
         return int(actions[0]), pis[0], obs[0]
 
     def select_action(self, gamestate):                # self_play.py:689-703: fresh tree at `gamestate`, no noise, tau 0.12
