@@ -276,6 +276,34 @@ int tg_sp_gumbel_target(tg_ctx* ctx, const int32_t* counts /*[G][A]*/, const uin
 /* Cumulative since tg_create: root selections made in Gumbel moves, and how many of them found no child at v(t). */
 int tg_sp_gumbel_stats(tg_ctx* ctx, uint64_t* root_selections, uint64_t* fallback_selections);
 
+/* ---- search ownership (KataGo's ownership map) -------------------------------------------------------------------
+ * on != 0 (off is the default): every simulation tg_sp_absorb backs up also adds the ownership head's row of its leaf, turned to
+ * Black's point of view, to a per-game accumulator: own_sum[g][p] = f32(own_sum[g][p] + s * own[row][p]), s = +1 when Black is to
+ * move at the leaf (the root's side to move flipped by the parity of the path's moves), else -1; paths in the order tg_sp_absorb
+ * handles them, wave after wave.  own_n[g] counts them.  What contributes is exactly what tg_sp_absorb backs up: not the duplicate
+ * leaf of a wave (dropped, self_play.py:732-734), not a simulation that ends the game (backed up in tg_sp_collect without a
+ * network row), not the root's own evaluation (tg_sp_expand_roots), not evaluations inherited with a reused sub-tree.  Both are
+ * cleared by tg_sp_begin_move / tg_sp_begin_move_games (the mean is over ONE move's search), by tg_sp_reset (the slots it restarts),
+ * tg_sp_reset_from and tg_sp_restore; they are not part of a snapshot, and neither is the switch.  The mode does not steer the
+ * search: visits, moves and RNG streams are those of the same search with the mode off.  Turning it on allocates the accumulators
+ * and [n_games * parallel_readouts][S*S] floats for the pending batch's ownership rows (once; they stay with the context when the
+ * mode is turned off again); while it is on tg_sp_eval / tg_sp_search
+ * make the forward write its ownership head (mapped back under the symmetry modes), and a host evaluator delivers through
+ * tg_sp_set_eval_own -- plain tg_sp_set_eval is TG_ERR_STATE.  TG_ERR_STATE while an evaluation batch (leaves or roots) is pending, and while an evaluation
+ * cache is attached: the cache stores policy and value only, so a hit has no ownership to give (tg_sp_eval_cache with entries > 0
+ * is refused in turn while the mode is on). */
+int tg_sp_search_ownership(tg_ctx* ctx, int on);
+int tg_sp_search_ownership_get(tg_ctx* ctx, int* on);
+/* tg_sp_set_eval with the ownership rows of the batch, each from the point of view of the side to move in that row's position
+ * (what model.main_prediction returns).  TG_ERR_STATE while the mode is off. */
+int tg_sp_set_eval_own(tg_ctx* ctx, const float* policy /*[n_rows][A]*/, const float* value /*[n_rows]*/,
+                       const float* own /*[n_rows][S*S]*/, int32_t n_rows);
+/* mean[g][p] = own_sum[g][p] / (float)own_n[g] (one float32 division; +1 Black ... -1 White; all 0 while own_n[g] == 0),
+ * n[g] = own_n[g], score_lead[g] = (mean[g][0] + mean[g][1] + ..., sequential float32 in point order) - komi: Black's lead, the
+ * sign of tg_sp_final's score.  A read-out like tg_sp_root_children: nothing changes, legal at any move boundary.  TG_ERR_STATE
+ * before the first tg_sp_reset and while the mode is off.  Any pointer may be NULL. */
+int tg_sp_root_ownership(tg_ctx* ctx, float* mean /*[G][S*S] or NULL*/, int32_t* n /*[G] or NULL*/, float* score_lead /*[G] or NULL*/);
+
 /* One random_sample() from each game's stream: the draw inside np.random.choice(A, p=) (self_play.py:683). */
 int tg_sp_draw_uniform(tg_ctx* ctx, double* u /*[G]*/, const uint8_t* mask);
 int tg_sp_rng_state(tg_ctx* ctx, int game, tg_mt19937* out);

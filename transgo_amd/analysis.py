@@ -19,7 +19,7 @@ def vertex(action, board_size):
     return f"{_COLUMNS[action % S]}{S - action // S}"
 
 
-def analyse(engine, states, num_simulation=0, depth=16, symmetry=None, eval_cache_entries=None):
+def analyse(engine, states, num_simulation=0, depth=16, symmetry=None, eval_cache_entries=None, ownership=False):
     """Search every position of `states` ([N, state_size] uint8 blobs of transgo_amd.environment.GoEnv) in evaluation mode -- a
     fresh root, no root noise, as select_action's prologue (self_play.py:689-700) -- and read the trees out.  The engine's games
     are re-rooted (`reset_from`), so whatever they held is gone; the engine must have been `reset` once before (that seeds the
@@ -36,19 +36,34 @@ def analyse(engine, states, num_simulation=0, depth=16, symmetry=None, eval_cach
     eval_cache_entries: an int gives the engine an exact evaluation cache of that many entries first (SelfPlayEngine.set_eval_cache;
     0 frees it) and leaves it in place for later calls -- the same results, fewer network rows when positions repeat within or
     across the searched trees.  None = the engine as it is.
+    ownership: True searches with search ownership on (SelfPlayEngine.set_search_ownership) for this call -- the engine's own switch
+    is put back afterwards -- and every record gains
+      ownership        float32[S, S]  mean of the ownership head over the evaluations the search backed up, +1 black ... -1 white
+      ownership_evals  int            how many evaluations that mean rests on (0: the map is all zero)
+      score_lead       float          float32 sum of the map in point order - komi: black's lead as the search sees it
+    The engine must then have no evaluation cache (it stores no ownership): asking for both raises ValueError.
     """
     states = np.ascontiguousarray(states, np.uint8)
     if states.ndim != 2:
         raise ValueError("states must be [N, state_size]")
+    if ownership and eval_cache_entries:
+        raise ValueError("analyse: ownership=True and eval_cache_entries > 0: the evaluation cache stores policy and value only, so a "
+                         "position it serves has no ownership to add to the mean")
     if eval_cache_entries is not None:
         engine.set_eval_cache(eval_cache_entries)
     if symmetry is not None:
         old = engine.get_symmetry()
         engine.set_symmetry(symmetry, old[1] if symmetry == "position" and old[0] == 2 else 0)
         try:
-            return analyse(engine, states, num_simulation, depth)
+            return analyse(engine, states, num_simulation, depth, ownership=ownership)
         finally:
             engine.set_symmetry(("none", "fixed", "position", "mean8")[old[0]], old[1])
+    if ownership and not engine.get_search_ownership():
+        engine.set_search_ownership(True)                  # (an attached evaluation cache makes the library refuse, with the reason)
+        try:
+            return analyse(engine, states, num_simulation, depth, ownership=True)
+        finally:
+            engine.set_search_ownership(False)
     G, N = engine.G, states.shape[0]
     out = []
     for lo in range(0, N, G):
@@ -60,6 +75,7 @@ def analyse(engine, states, num_simulation=0, depth=16, symmetry=None, eval_cach
         engine.search(selfplay=False, num_simulation=num_simulation)
         rc = engine.root_children()
         act, vis, _, ln = engine.principal_variation(depth)
+        so = engine.root_ownership() if ownership else None
         for g in range(k):
             present = (rc["flags"][g] & engine.CHILD_PRESENT) != 0
             n, w = rc["n"][g], rc["w"][g]
@@ -71,6 +87,8 @@ def analyse(engine, states, num_simulation=0, depth=16, symmetry=None, eval_cach
             m = max(int(ln[g]), 0)
             out.append(dict(visits=n.copy(), prior=rc["prior"][g].copy(), q=q, legal=present, status=int(rc["status"][g]),
                             root_value=root_value, pv=[int(a) for a in act[g, :m]], pv_visits=[int(v) for v in vis[g, :m]]))
+            if so is not None:
+                out[-1].update(ownership=so["mean"][g].copy(), ownership_evals=int(so["n"][g]), score_lead=float(so["score_lead"][g]))
     return out
 
 
@@ -132,11 +150,16 @@ def playout_ownership(env, states, playouts=64, seed=0):
 
 def format_ownership(record, board_size):
     """The territory map of one `playout_ownership` record as a board of percentages (+100 black ... -100 white), with the mean
-    score and black's win rate on top."""
+    score and black's win rate on top.  An `analyse(..., ownership=True)` record prints the same board from its search ownership,
+    under the number of evaluations and the score lead."""
     S = int(board_size)
-    t = np.asarray(record["territory"]).reshape(S, S)
-    lines = [f"playouts {int(record['playouts'])}   mean score {record['score']:+.2f}   black wins {100 * record['black_win']:.1f}%",
-             "    " + " ".join(f"{c:>4}" for c in _COLUMNS[:S])]
+    if "territory" in record:
+        t = np.asarray(record["territory"]).reshape(S, S)
+        head = f"playouts {int(record['playouts'])}   mean score {record['score']:+.2f}   black wins {100 * record['black_win']:.1f}%"
+    else:
+        t = np.asarray(record["ownership"]).reshape(S, S)
+        head = f"search ownership over {int(record['ownership_evals'])} evaluations   score lead {record['score_lead']:+.2f}"
+    lines = [head, "    " + " ".join(f"{c:>4}" for c in _COLUMNS[:S])]
     for y in range(S):
         lines.append(f"{S - y:>3} " + " ".join(f"{int(round(100 * v)):>+4d}" for v in t[y]))
     return "\n".join(lines)
@@ -146,7 +169,8 @@ def format_analysis(record, board_size, top=5, ownership=None):
     """A table of the `top` candidate moves of one `analyse` record: one line per candidate in descending visits (ties: ascending
     action) with its vertex, visits, q, prior and its line -- the principal variation for the move that heads it, the move alone
     for the others.  A q that is NaN (never visited) prints as '-'.  `ownership`: a `playout_ownership` record of the same
-    position, printed underneath (format_ownership)."""
+    position, printed underneath (format_ownership).  A record that carries its own search ownership (analyse(..., ownership=True))
+    prints that board too."""
     visits, prior, q = np.asarray(record["visits"]), np.asarray(record["prior"]), np.asarray(record["q"])
     legal = np.asarray(record["legal"]) if "legal" in record else (visits > 0) | (prior > 0)
     cand = sorted(np.flatnonzero(legal), key=lambda a: (-int(visits[a]), int(a)))[:max(int(top), 0)]
@@ -159,6 +183,8 @@ def format_analysis(record, board_size, top=5, ownership=None):
         line = pv if pv and pv[0] == a else [a]
         lines.append(f"{vertex(a, board_size):<5}{int(visits[a]):>8}{qs:>8}{float(prior[a]):>8.4f}  "
                      + " ".join(vertex(m, board_size) for m in line))
+    if "ownership" in record:
+        lines.append(format_ownership(record, board_size))
     if ownership is not None:
         lines.append(format_ownership(ownership, board_size))
     return "\n".join(lines)

@@ -47,6 +47,9 @@ class Config:
                                                  # improved policy as the target.  Only 0 keeps parity with the reference
         self.gumbel_c_visit = 50.0               # sigma(q) = (c_visit + max visits) * c_scale * q
         self.gumbel_c_scale = 1.0
+        self.search_ownership = False            # True: every search also averages the ownership head over the positions it evaluates
+                                                 # (SelfPlayEngine.root_ownership; analysis).  The search itself is unchanged; refused
+                                                 # together with eval_cache_entries > 0.  policy_evaluate ignores it
         self.batch_size = 2048
         self.train_play_ratio = 7500 / 100000    # configure.py:61
         self.adjust_train_play_ratio = True
@@ -62,6 +65,9 @@ class Config:
         check_params(self.gumbel_m, self.gumbel_c_visit, self.gumbel_c_scale)
         if self.gumbel_m > 0 and self.forced_playouts_k > 0:
             raise ValueError("gumbel_m > 0 and forced_playouts_k > 0: both are rules for the same root, choose one")
+        if self.search_ownership and self.eval_cache_entries:
+            raise ValueError("search_ownership and eval_cache_entries > 0: the evaluation cache stores policy and value only, so a hit "
+                             "has no ownership to give; choose one")
 
     def epsilon_by_frame(self, game_step):       # configure.py:75-79
         return 0.65 + (1.0 - 0.65) * math.exp(-1. * game_step / 10)

@@ -92,6 +92,13 @@ struct Engine {
     int32_t* d_gumbel_target = nullptr;   // [G][A] by action: the counts staged by tg_sp_gumbel_target
     uint8_t* d_gumbel_staged = nullptr;   // [G]    ... and for which games
     std::vector<double> h_gumbel;    // [G][A] the variates of one move (host)
+    // Search ownership: context state, off by default -- only while it is on do these buffers exist, is k_absorb_own
+    // launched in k_absorb's place and does the forward write its ownership head for the pending batch.  The accumulators are
+    // cleared by every begin_move, reset and restore; they are not part of a snapshot.
+    bool own_on = false;
+    float* d_own = nullptr;          // [rows_cap][P] ownership rows of the pending batch (side to move's point of view)
+    float* d_own_sum = nullptr;      // [G][P] sum over the move's absorbed simulations, Black's point of view
+    int32_t* d_own_n = nullptr;      // [G]    how many simulations the sum holds
     Net* net = nullptr;
     EvalCache* cache = nullptr;      // tg_sp_eval_cache: nullptr = every pending row goes through the network (nothing else is launched)
     // HIP-event timing of the tree stage (k_collect, k_absorb) on the engine's stream, switched by tg_prof_enable
@@ -104,11 +111,17 @@ int eval_cache_run(tg_ctx* ctx, int rows);      // the pending batch: probe, in-
 void eval_cache_invalidate(tg_ctx* ctx);        // the evaluator changed (weights, precision, symmetry): no entry made so far may hit again
 void eval_cache_destroy(tg_ctx* ctx);
 
+// engine.hip -- search ownership: the accumulators of the games with d_mask[g] != 0 (nullptr = every game) := 0, on
+// ctx->stream; nothing is launched while the mode is off
+int own_clear(tg_ctx* ctx, const uint8_t* d_mask);
+
 }  // namespace tg
 
 extern "C" int tg_net_forward(tg_ctx* ctx, int rows);   // pending batch (obs_bits through row_slot) -> policy[rows], value[rows] on ctx->stream
 // the same for `rows` rows listed in `slot` (entries of obs_bits), outputs row-indexed into the caller's buffers of >= rows rows
 extern "C" int tg_net_forward_rows(tg_ctx* ctx, int rows, const int32_t* slot, float* policy, float* value);
+// ... and with the ownership head written too: own[rows][P], the side to move's point of view (search ownership)
+extern "C" int tg_net_forward_rows_own(tg_ctx* ctx, int rows, const int32_t* slot, float* policy, float* value, float* own);
 extern "C" void tg_net_destroy(tg_ctx* ctx);
 extern "C" int tg_net_adopt_ready(tg_ctx* ctx);         // tg_sp_begin_move: a completed background weight refresh becomes the live set
 extern "C" int tg_net_load_arch(tg_ctx* ctx, const char* arch, const float* blob, size_t n_floats, int rows_cap);

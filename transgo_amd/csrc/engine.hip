@@ -590,8 +590,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(S == 9 ? 4 :
     collect_body<S, COLLECT_GUMBEL>(d, 0.0, nullptr, nullptr, gd);
 }
 
-template <int S>
-__global__ __launch_bounds__(64) void k_absorb(EngineDev d) {
+// OWN (search ownership): every simulation backed up here also adds its leaf's ownership row, turned to Black's point of
+// view, into the game's accumulator row.  The head speaks for the side to move at the leaf (self_play.py:929-967), which is the
+// root's next_player flipped by the parity of len - 1.  A lane owns the points lane, lane + 64, ...; paths come in q order: the order
+// of the float32 additions is fixed, there are no atomics and nothing crosses lanes.
+template <int S, bool OWN>
+__device__ __forceinline__ void absorb_body(const EngineDev& d, const float* __restrict__ own, float* __restrict__ own_sum, int32_t* own_n) {
     constexpr int HS = TreeGeo<S>::HS;
     __shared__ float pol_s[Geo<S>::A + 64];
     const int g = blockIdx.x, lane = lane_id();
@@ -602,6 +606,12 @@ __global__ __launch_bounds__(64) void k_absorb(EngineDev d) {
     NodeRec* arena = d.arena;
     const int* paths = d.path_nodes + (size_t)g * sc.R * sc.maxd;
     unsigned long long sims = 0;
+    bool root_black = false;
+    float* acc = nullptr;
+    if (OWN) {
+        root_black = hdr_of<S>(arena, arena[c->root].block)->st.next_player == 1;
+        acc = own_sum + (size_t)g * Geo<S>::P;
+    }
     for (int q = 0; q < npaths; ++q) {                                 // self_play.py:651-654
         const int* path = paths + q * sc.maxd;
         const int len = d.path_len[(size_t)g * sc.R + q], row = d.game_off[g] + d.path_row[(size_t)g * sc.R + q];
@@ -636,8 +646,56 @@ __global__ __launch_bounds__(64) void k_absorb(EngineDev d) {
         for (int dd = lane; dd < len; dd += 64) backup_node(&arena[path[dd]], ((len - 1 - dd) & 1) ? -val : val);
         __syncthreads();
         ++sims;
+        if (OWN) {
+            const float* orow = own + (size_t)row * Geo<S>::P;
+            const bool black = root_black == (((len - 1) & 1) == 0);    // Black is to move at the leaf
+            for (int p = lane; p < Geo<S>::P; p += 64) { const float o = orow[p]; acc[p] = acc[p] + (black ? o : -o); }
+        }
     }
-    if (lane == 0) { c->n_paths = 0; c->sims += sims; }
+    if (lane == 0) {
+        c->n_paths = 0; c->sims += sims;
+        if (OWN) own_n[g] += (int32_t)sims;
+    }
+}
+
+template <int S>
+__global__ __launch_bounds__(64) void k_absorb(EngineDev d) {
+    absorb_body<S, false>(d, nullptr, nullptr, nullptr);
+}
+template <int S>
+__global__ __launch_bounds__(64) void k_absorb_own(EngineDev d, const float* own, float* own_sum, int32_t* own_n) {
+    absorb_body<S, true>(d, own, own_sum, own_n);
+}
+
+// the accumulators of the games with mask[g] != 0 (nullptr = every game) := 0; a block per game
+__global__ __launch_bounds__(64) void k_own_clear(float* own_sum, int32_t* own_n, const uint8_t* mask, int P) {
+    const int g = blockIdx.x;
+    if (mask && !mask[g]) return;
+    for (int p = threadIdx.x; p < P; p += 64) own_sum[(size_t)g * P + p] = 0.f;
+    if (threadIdx.x == 0) own_n[g] = 0;
+}
+
+// tg_sp_root_ownership: mean = own_sum / (float)own_n (one float32 division; all 0 while own_n == 0) and Black's score lead = the
+// sequential float32 sum of the means in point order - komi (tg_sp_final's sign).  One lane per game does the sum.
+template <int S>
+__global__ __launch_bounds__(64) void k_root_ownership(const float* own_sum, const int32_t* own_n, float komi, float* mean, int32_t* n_out, float* lead) {
+    constexpr int P = Geo<S>::P;
+    __shared__ float mean_s[P];
+    const int g = blockIdx.x, lane = lane_id();
+    const int n = own_n[g];
+    const float fn = (float)n;
+    for (int p = lane; p < P; p += 64) {
+        const float m = n > 0 ? own_sum[(size_t)g * P + p] / fn : 0.f;
+        mean_s[p] = m;
+        mean[(size_t)g * P + p] = m;
+    }
+    __syncthreads();
+    if (lane == 0) {
+        float s = mean_s[0];
+        for (int p = 1; p < P; ++p) s = s + mean_s[p];
+        n_out[g] = n;
+        lead[g] = s - komi;
+    }
 }
 
 template <int S>
@@ -1476,11 +1534,20 @@ int begin_move(tg_ctx* ctx, const char* who, bool noise_all, const uint8_t* nois
     { int rc = rng_to_device(ctx); if (rc) return rc; }
     TG_LAUNCH(ctx, k_begin, G, e->dev, sims, d_sims, d_skip, e->d_forced, d_noise_g, (noise_all && e->forced_k > 0.0) ? 1 : 0);
     if (gumbel) TG_LAUNCH(ctx, k_begin_gumbel, G, e->dev, e->d_gumbel, d_noise_g, e->d_gumbel_n0, e->d_gumbel_N0, e->d_gumbel_staged);
+    { int rc = own_clear(ctx, nullptr); if (rc) return rc; }           // search ownership: the mean is over this move's search
     TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return TG_OK;
 }
 
 }  // namespace
+
+int tg::own_clear(tg_ctx* ctx, const uint8_t* d_mask) {
+    Engine* e = ctx->eng;
+    if (!e->own_on) return TG_OK;
+    hipLaunchKernelGGL(k_own_clear, dim3(e->G), dim3(64), 0, ctx->stream, e->d_own_sum, e->d_own_n, d_mask, ctx->P);
+    TG_HIP(ctx, hipGetLastError());
+    return TG_OK;
+}
 
 extern "C" {
 
@@ -1609,7 +1676,8 @@ void tg_engine_destroy(tg_ctx* ctx) {
     void* ptrs[] = {e->dev.arena, e->dev.ring, e->dev.pool, e->dev.chunk_ids, e->dev.ctl, e->dev.rng, e->dev.path_nodes, e->dev.path_len, e->dev.path_row, e->dev.row_slot,
                     e->dev.obs_bits, e->dev.game_nslot, e->dev.game_off, e->dev.game_act, e->dev.policy, e->dev.value, e->dev.counters, e->d_noise, e->d_i32, e->d_f32, e->d_u8,
                     e->d_fin, e->dev.hist_obs, e->dev.hist_cnt, e->dev.hist_pl, e->dev.ply_skip, e->d_forced, e->d_forced_stat,
-                    e->d_gumbel, e->d_gumbel_stat, e->d_gumbel_n0, e->d_gumbel_N0, e->d_gumbel_target, e->d_gumbel_staged};
+                    e->d_gumbel, e->d_gumbel_stat, e->d_gumbel_n0, e->d_gumbel_N0, e->d_gumbel_target, e->d_gumbel_staged,
+                    e->d_own, e->d_own_sum, e->d_own_n};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (e->h_rng) (void)hipHostFree(e->h_rng);
     e->obs_f32.release(); e->readout.release(); e->snap_tab.release(); e->snap_stage.release(); e->hv_obs.release(); e->hv_cnt.release(); e->hv_z.release(); e->hv_own.release(); e->hv_pl.release(); e->hv_game.release();
@@ -1651,6 +1719,7 @@ int tg_sp_reset(tg_ctx* ctx, const uint32_t* seeds, const uint8_t* mask) {
         if (!mask) { TG_HIP(ctx, hipMemsetAsync(e->d_gumbel, 0, (size_t)G, ctx->stream)); }
         else hipLaunchKernelGGL(k_clear_forced, dim3((G + 255) / 256), dim3(256), 0, ctx->stream, e->d_gumbel, (const uint8_t*)d_mask, G);
     }
+    { int rc = own_clear(ctx, d_mask); if (rc) return rc; }            // search ownership: a restarted game has searched nothing
     if (!mask) hipLaunchKernelGGL(k_pool_init, dim3(64), dim3(256), 0, ctx->stream, e->dev, 0);
     else {
         hipLaunchKernelGGL(k_release, dim3(G), dim3(64), 0, ctx->stream, e->dev, (const uint8_t*)d_mask);
@@ -1685,6 +1754,7 @@ int tg_sp_reset_from(tg_ctx* ctx, const void* states, const uint8_t* mask) {
     TG_HIP(ctx, hipMemsetAsync(e->dev.ply_skip, 0, (size_t)G, ctx->stream));
     TG_HIP(ctx, hipMemsetAsync(e->d_forced, 0, (size_t)G, ctx->stream));          // (every slot is restarted or parked)
     if (e->gumbel_m > 0) TG_HIP(ctx, hipMemsetAsync(e->d_gumbel, 0, (size_t)G, ctx->stream));
+    { int rc = own_clear(ctx, nullptr); if (rc) return rc; }
     // (unmasked slots are parked by k_reset and keep the one chunk they own until their next reset)
     hipLaunchKernelGGL(k_release, dim3(G), dim3(64), 0, ctx->stream, e->dev, (const uint8_t*)d_mask);
     hipLaunchKernelGGL(k_pool_publish, dim3(1), dim3(1), 0, ctx->stream, e->dev);
@@ -1744,9 +1814,25 @@ int tg_sp_set_eval(tg_ctx* ctx, const float* policy, const float* value, int32_t
     NEED_ENGINE(ctx);
     Engine* e = ctx->eng;
     if (e->batch_kind == BATCH_NONE) TG_FAIL(ctx, TG_ERR_STATE, "tg_sp_set_eval: no batch pending");
+    if (e->own_on) TG_FAIL(ctx, TG_ERR_STATE, "tg_sp_set_eval: search ownership is on (tg_sp_search_ownership): every row needs its ownership too, use tg_sp_set_eval_own");
     if (n_rows < 0 || n_rows > e->rows_cap) return TG_ERR_ARG;
     TG_HIP(ctx, hipMemcpyAsync(e->dev.policy, policy, sizeof(float) * (size_t)n_rows * ctx->A, hipMemcpyHostToDevice, ctx->stream));
     TG_HIP(ctx, hipMemcpyAsync(e->dev.value, value, sizeof(float) * (size_t)n_rows, hipMemcpyHostToDevice, ctx->stream));
+    TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    e->batch_ready = true;
+    return TG_OK;
+}
+
+int tg_sp_set_eval_own(tg_ctx* ctx, const float* policy, const float* value, const float* own, int32_t n_rows) {
+    NEED_ENGINE(ctx);
+    Engine* e = ctx->eng;
+    if (e->batch_kind == BATCH_NONE) TG_FAIL(ctx, TG_ERR_STATE, "tg_sp_set_eval_own: no batch pending");
+    if (!e->own_on) TG_FAIL(ctx, TG_ERR_STATE, "tg_sp_set_eval_own: search ownership is off (tg_sp_search_ownership): use tg_sp_set_eval");
+    if (n_rows < 0 || n_rows > e->rows_cap) return TG_ERR_ARG;
+    if (n_rows > 0 && (!policy || !value || !own)) TG_FAIL(ctx, TG_ERR_ARG, "tg_sp_set_eval_own: policy, value and own must not be NULL");
+    TG_HIP(ctx, hipMemcpyAsync(e->dev.policy, policy, sizeof(float) * (size_t)n_rows * ctx->A, hipMemcpyHostToDevice, ctx->stream));
+    TG_HIP(ctx, hipMemcpyAsync(e->dev.value, value, sizeof(float) * (size_t)n_rows, hipMemcpyHostToDevice, ctx->stream));
+    TG_HIP(ctx, hipMemcpyAsync(e->d_own, own, sizeof(float) * (size_t)n_rows * ctx->P, hipMemcpyHostToDevice, ctx->stream));
     TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     e->batch_ready = true;
     return TG_OK;
@@ -1759,7 +1845,9 @@ int tg_sp_eval(tg_ctx* ctx) {
     int32_t cnt[CNT_N];
     int rc = read_counters(ctx, cnt);
     if (rc) return rc;
-    rc = e->cache ? eval_cache_run(ctx, cnt[CNT_ROWS]) : tg_net_forward(ctx, cnt[CNT_ROWS]);
+    rc = e->cache ? eval_cache_run(ctx, cnt[CNT_ROWS])
+         : e->own_on ? tg_net_forward_rows_own(ctx, cnt[CNT_ROWS], e->dev.row_slot, e->dev.policy, e->dev.value, e->d_own)
+                     : tg_net_forward(ctx, cnt[CNT_ROWS]);
     if (rc) return rc;
     e->batch_ready = true;
     return TG_OK;
@@ -1818,7 +1906,8 @@ int tg_sp_absorb(tg_ctx* ctx) {
     if (!e->batch_ready) TG_FAIL(ctx, TG_ERR_STATE, "tg_sp_absorb: batch not evaluated");
     const bool timed = e->tprof && e->tev_used + 2 <= e->tev.size();
     if (timed) { TG_HIP(ctx, hipEventRecord(e->tev[e->tev_used], ctx->stream)); }
-    TG_LAUNCH(ctx, k_absorb, e->G, e->dev);
+    if (e->own_on) TG_LAUNCH(ctx, k_absorb_own, e->G, e->dev, (const float*)e->d_own, e->d_own_sum, e->d_own_n);
+    else TG_LAUNCH(ctx, k_absorb, e->G, e->dev);
     if (timed) { TG_HIP(ctx, hipEventRecord(e->tev[e->tev_used + 1], ctx->stream)); e->tev_kind[e->tev_used / 2] = 1; e->tev_used += 2; }
     e->batch_kind = BATCH_NONE; e->batch_ready = false;
     return TG_OK;
@@ -1836,7 +1925,11 @@ int tg_sp_search(tg_ctx* ctx, int32_t* n_waves) {
         if (rc) return rc;
         if (rows > 0) {
             if (g_trace_launch) { fprintf(stderr, "[tg %ld] network forward, %d rows\n", ++g_trace_seq, rows); fflush(stderr); }
-            rc = ctx->eng->cache ? eval_cache_run(ctx, rows) : tg_net_forward(ctx, rows); if (rc) return rc; ctx->eng->batch_ready = true;
+            Engine* e = ctx->eng;
+            rc = e->cache ? eval_cache_run(ctx, rows)
+                 : e->own_on ? tg_net_forward_rows_own(ctx, rows, e->dev.row_slot, e->dev.policy, e->dev.value, e->d_own) : tg_net_forward(ctx, rows);
+            if (rc) return rc;
+            e->batch_ready = true;
             if (g_trace_launch) TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
         }
         rc = tg_sp_absorb(ctx);
@@ -1923,6 +2016,50 @@ int tg_sp_pv(tg_ctx* ctx, int depth, int32_t* action, int32_t* n, float* w, int3
     if (n) TG_HIP(ctx, hipMemcpyAsync(n, d_n, sizeof(int32_t) * GD, hipMemcpyDeviceToHost, ctx->stream));
     if (w) TG_HIP(ctx, hipMemcpyAsync(w, d_w, sizeof(float) * GD, hipMemcpyDeviceToHost, ctx->stream));
     if (len) TG_HIP(ctx, hipMemcpyAsync(len, d_len, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
+    TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return TG_OK;
+}
+
+// ---- search ownership -------------------------------------------------------------------------------------------
+int tg_sp_search_ownership(tg_ctx* ctx, int on) {
+    if (!ctx) return TG_ERR_ARG;
+    if (!ctx->eng || ctx->eng->G <= 0) TG_FAIL(ctx, TG_ERR_ARG, "tg_sp_search_ownership: the context has no self-play engine (n_games = 0)");
+    Engine* e = ctx->eng;
+    // any pending batch, roots included: the switch decides which of tg_sp_set_eval / tg_sp_set_eval_own a host evaluator may call
+    if (e->batch_kind != BATCH_NONE) TG_FAIL(ctx, TG_ERR_STATE, "tg_sp_search_ownership: an evaluation batch is pending");
+    if (on && e->cache)
+        TG_FAIL(ctx, TG_ERR_STATE, "tg_sp_search_ownership: an evaluation cache is attached (tg_sp_eval_cache); it stores policy and value only, so a hit has no ownership to give");
+    TG_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    if (on) {                                                          // each buffer once; they stay with the context when the mode goes off
+        const size_t G = (size_t)e->G, P = (size_t)ctx->P;
+        if (!e->d_own) TG_HIP(ctx, hipMalloc((void**)&e->d_own, sizeof(float) * (size_t)e->rows_cap * P));
+        if (!e->d_own_sum) TG_HIP(ctx, hipMalloc((void**)&e->d_own_sum, sizeof(float) * G * P));
+        if (!e->d_own_n) TG_HIP(ctx, hipMalloc((void**)&e->d_own_n, sizeof(int32_t) * G));
+    }
+    const bool was = e->own_on;
+    e->own_on = on != 0;
+    if (e->own_on && !was) { int rc = own_clear(ctx, nullptr); if (rc) return rc; TG_HIP(ctx, hipStreamSynchronize(ctx->stream)); }
+    return TG_OK;
+}
+
+int tg_sp_search_ownership_get(tg_ctx* ctx, int* on) {
+    if (!ctx || !ctx->eng || !on) return TG_ERR_ARG;
+    *on = ctx->eng->own_on ? 1 : 0;
+    return TG_OK;
+}
+
+int tg_sp_root_ownership(tg_ctx* ctx, float* mean, int32_t* n, float* score_lead) {
+    NEED_READOUT(ctx, "tg_sp_root_ownership");
+    Engine* e = ctx->eng;
+    if (!e->own_on) TG_FAIL(ctx, TG_ERR_STATE, "tg_sp_root_ownership: search ownership is off (call tg_sp_search_ownership(ctx, 1) before the search)");
+    const size_t G = (size_t)e->G, GP = G * ctx->P;
+    // staging: mean f32[G][P] | score lead f32[G] | n i32[G]
+    if (e->readout.reserve(GP * 4 + G * 8)) TG_FAIL(ctx, TG_ERR_HIP, "hipMalloc failed");
+    float* d_mean = (float*)e->readout.p; float* d_lead = d_mean + GP; int32_t* d_n = (int32_t*)(d_lead + G);
+    TG_LAUNCH(ctx, k_root_ownership, e->G, (const float*)e->d_own_sum, (const int32_t*)e->d_own_n, ctx->cfg.komi, d_mean, d_n, d_lead);
+    if (mean) TG_HIP(ctx, hipMemcpyAsync(mean, d_mean, sizeof(float) * GP, hipMemcpyDeviceToHost, ctx->stream));
+    if (n) TG_HIP(ctx, hipMemcpyAsync(n, d_n, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));
+    if (score_lead) TG_HIP(ctx, hipMemcpyAsync(score_lead, d_lead, sizeof(float) * G, hipMemcpyDeviceToHost, ctx->stream));
     TG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return TG_OK;
 }

@@ -301,6 +301,8 @@ int tg_sp_eval_cache(tg_ctx* ctx, uint64_t entries) {
     TG_HIP(ctx, hipSetDevice(ctx->cfg.device));
     Engine* e = ctx->eng;
     if (e->batch_kind != BATCH_NONE) TG_FAIL(ctx, TG_ERR_STATE, "tg_sp_eval_cache: an evaluation batch is pending");
+    if (entries && e->own_on)
+        TG_FAIL(ctx, TG_ERR_STATE, "tg_sp_eval_cache: search ownership is on (tg_sp_search_ownership); the cache stores policy and value only, so a hit has no ownership to give");
     const int W = e->dev.obs_words, A = ctx->A;
     if (entries && W > 64 * kEcLaneWords) TG_FAIL(ctx, TG_ERR_ARG, "tg_sp_eval_cache: rows of more than 192 words are not supported");
     if (entries > (1ull << 31)) TG_FAIL(ctx, TG_ERR_ARG, "tg_sp_eval_cache: at most 2^31 entries");

@@ -2842,11 +2842,16 @@ int tg_net_forward(tg_ctx* ctx, int rows) {
 }
 
 int tg_net_forward_rows(tg_ctx* ctx, int rows, const int32_t* slot, float* policy, float* value) {
+    return tg_net_forward_rows_own(ctx, rows, slot, policy, value, nullptr);
+}
+
+// own == nullptr: the ownership head is not written (k_heads skips it), as the search has always run it
+int tg_net_forward_rows_own(tg_ctx* ctx, int rows, const int32_t* slot, float* policy, float* value, float* own) {
     Engine* e = ctx->eng;
     if (!e || !e->net) TG_FAIL(ctx, TG_ERR_STATE, "no network weights loaded (tg_net_load)");
     Net* n = e->net;
     n->in_bits = e->dev.obs_bits; n->in_slot = slot; n->in_words = e->dev.obs_words;
-    const int rc = forward_sym(ctx, n, nullptr, rows, policy, value, nullptr);
+    const int rc = forward_sym(ctx, n, nullptr, rows, policy, value, own);
     n->in_bits = nullptr; n->in_slot = nullptr;
     return rc;
 }

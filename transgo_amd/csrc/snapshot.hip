@@ -453,6 +453,7 @@ int tg_sp_restore(tg_ctx* ctx, const void* in, uint64_t bytes, int device_mem) {
     TG_HIP(ctx, hipMemsetAsync(d.ply_skip, 0, (size_t)e->G, st));      // a snapshot is a move boundary: no record switch is in flight
     TG_HIP(ctx, hipMemsetAsync(e->d_forced, 0, (size_t)e->G, st));     // ... and no forced move (a snapshot inside a move's search is refused)
     TG_HIP(ctx, hipMemsetAsync(e->d_gumbel, 0, (size_t)e->G, st));     // ... nor a Gumbel move
+    { int rc2 = own_clear(ctx, nullptr); if (rc2) return rc2; }        // search ownership is per search and not part of a snapshot
     int32_t *coff, *poff; int32_t tot[3];
     rc = run_scan(ctx, &coff, &poff, tot);                             // the offsets, from the control records just restored
     if (rc) return rc;

@@ -114,7 +114,7 @@ class SelfPlayEngine:
                  wu_loss=2, komi=7.5, max_step=120, encode_dim=10, net_blocks=6, net_filters=128, arena_slots=0,
                  device=0, evaluator=None, net_precision="f32", record_games=True, pool_slots=0, eval_symmetry="none",
                  symmetry_seed=0, eval_cache_entries=0, forced_playouts_k=0.0, gumbel_m=0, gumbel_c_visit=50.0,
-                 gumbel_c_scale=1.0):
+                 gumbel_c_scale=1.0, search_ownership=False):
         cfg = _lib.default_config()
         cfg.record_games = 1 if record_games else 0       # per-move records in HBM for tg_sp_harvest (self-play); evaluation matches need none
         cfg.net_precision = {"f32": 0, "f16": 1, "f16r": 2, "f32x3": 3}[net_precision]
@@ -128,6 +128,7 @@ class SelfPlayEngine:
         self.num_simulation = num_simulation
         self.path_capacity = (max_step + 2 + 63) // 64 * 64      # SearchCfg::maxd: the deepest line principal_variation can return
         self.evaluator = evaluator           # None -> network on the GPU; callable(obs)->(policy, value) -> injected
+                                             # (-> (policy, value, own) while search ownership is on)
         self.finished = np.zeros(n_games, bool)      # slots that take no part in the next search (game over, parked, in error)
         self.errored = np.zeros(n_games, bool)       # slots parked by a tree-arena overflow (restart them with reset(mask))
         self.device = device
@@ -143,6 +144,9 @@ class SelfPlayEngine:
         self.gumbel_m, self.gumbel_c_visit, self.gumbel_c_scale = 0, 50.0, 1.0
         if gumbel_m:
             self.set_gumbel(gumbel_m, gumbel_c_visit, gumbel_c_scale)
+        self.search_ownership = False
+        if search_ownership:
+            self.set_search_ownership(True)
 
     def close(self):
         self.ctx.close()
@@ -271,6 +275,30 @@ class SelfPlayEngine:
             actions[gg] = gact[gg]; pis[gg] = pi[gg]
         return actions, pis, gg
 
+    # ---- search ownership (tg_sp_search_ownership) --------------------------------------------------------------
+    def set_search_ownership(self, on):
+        """on: every simulation a search backs up also adds its leaf's ownership (the network's third head), turned to Black's
+        point of view, to a per-game sum that root_ownership() reads as a mean -- KataGo's ownership map.  The search itself is
+        unchanged.  Off is the default.  Refused while an evaluation cache is attached (it stores no ownership) and while a leaf
+        batch is pending.  A host `evaluator` must return (policy, value, own) while it is on.  Context state: a snapshot carries
+        neither the switch nor the sums."""
+        self.ctx.call("tg_sp_search_ownership", 1 if on else 0)
+        self.search_ownership = bool(on)
+
+    def get_search_ownership(self):
+        on = ctypes.c_int()
+        self.ctx.call("tg_sp_search_ownership_get", ctypes.byref(on))
+        return bool(on.value)
+
+    def root_ownership(self):
+        """tg_sp_root_ownership after a search with the mode on: "mean" float32 [G, S, S], the mean ownership over the evaluations
+        the last search backed up (+1 Black ... -1 White), "n" int32 [G], how many those were (terminal simulations, the root's own
+        evaluation and a reused sub-tree's earlier evaluations are not among them; a mean over 0 is all 0), and "score_lead"
+        float32 [G] = float32 sum of the mean in point order - komi, Black's lead."""
+        mean = np.zeros((self.G, self.S, self.S), np.float32); n = np.zeros(self.G, np.int32); lead = np.zeros(self.G, np.float32)
+        self.ctx.call("tg_sp_root_ownership", _ptr(mean), _ptr(n), _ptr(lead))
+        return dict(mean=mean, n=n, score_lead=lead)
+
     # ---- evaluation of the pending batch --------------------------------------------------------------------------------
     def _evaluate(self, rows=None):
         if self.evaluator is None:
@@ -285,11 +313,20 @@ class SelfPlayEngine:
         obs = np.empty((rows, self.C, self.S, self.S), np.float32)
         self.ctx.call("tg_sp_batch_obs", _ptr(obs), rows)
         m, a = self._host_symmetry
-        policy, value = (self.evaluator(obs) if m == 0 else
-                         _symmetry.evaluate_with_symmetry(self.evaluator, obs, ("none", "fixed", "position", "mean8")[m], a))[:2]
+        out = (self.evaluator(obs) if m == 0 else
+               _symmetry.evaluate_with_symmetry(self.evaluator, obs, ("none", "fixed", "position", "mean8")[m], a))
+        policy, value = out[:2]
         policy = np.ascontiguousarray(policy, np.float32); value = np.ascontiguousarray(value, np.float32).reshape(-1)
         assert policy.shape == (rows, self.A) and value.shape == (rows,)
-        self.ctx.call("tg_sp_set_eval", _ptr(policy), _ptr(value), rows)
+        if not self.search_ownership:
+            self.ctx.call("tg_sp_set_eval", _ptr(policy), _ptr(value), rows)
+            return
+        if len(out) < 3 or out[2] is None:
+            raise ValueError("search ownership is on: the evaluator must return (policy, value, own) with own [rows, S*S] from the side "
+                             "to move's point of view, it returned a two-tuple")
+        own = np.ascontiguousarray(out[2], np.float32).reshape(rows, -1)
+        assert own.shape == (rows, self.P)
+        self.ctx.call("tg_sp_set_eval_own", _ptr(policy), _ptr(value), _ptr(own), rows)
 
     # ---- reference-shaped operations, G games at a time -------------------------------------------------------------------
     def reset(self, seeds, mask=None):

@@ -101,7 +101,8 @@ class BatchedSelfPlay:
             eval_cache_entries=getattr(config, "eval_cache_entries", 0) if eval_cache_entries is None else eval_cache_entries,
             forced_playouts_k=getattr(config, "forced_playouts_k", 0.0),
             gumbel_m=getattr(config, "gumbel_m", 0), gumbel_c_visit=getattr(config, "gumbel_c_visit", 50.0),
-            gumbel_c_scale=getattr(config, "gumbel_c_scale", 1.0))
+            gumbel_c_scale=getattr(config, "gumbel_c_scale", 1.0),
+            search_ownership=bool(getattr(config, "search_ownership", False)))
         self.seed_fn = seed_fn
         self.games_started = np.zeros(n_games, np.int64)
         self.seeds = np.zeros(n_games, np.uint32)          # seed of the game now running in each slot
@@ -397,6 +398,17 @@ class GroupedSelfPlay:
 
     def start(self, stagger=0):
         self._each(lambda p: p.start(stagger))
+
+    # search ownership (SelfPlayEngine.set_search_ownership): the switch reaches every group, the read-out is in job order
+    def set_search_ownership(self, on):
+        self._each(lambda p: p.engine.set_search_ownership(on))
+
+    def get_search_ownership(self):
+        return self.parts[0].engine.get_search_ownership()
+
+    def root_ownership(self):
+        parts = self._each(lambda p: p.engine.root_ownership())
+        return {k: np.concatenate([r[k] for r in parts]) for k in ("mean", "n", "score_lead")}
 
     def advance(self, selfplay=True, device=False, num_simulation=0):
         """One move of every game of every group; returns the groups' finished-game batches (records.Harvest or None), in group order."""
