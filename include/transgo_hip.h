@@ -350,6 +350,51 @@ int tg_sp_finished(tg_ctx* ctx, int32_t* n_games, int32_t* n_positions);
  * augmentation (self_play.py:943-965) is applied by the consumer (tg_replay_sample; transgo_amd.self_play.game_targets). */
 int tg_sp_harvest(tg_ctx* ctx, uint32_t* obs_bits, int32_t* counts, float* z, int8_t* own, uint8_t* player, int device_out,
                   int32_t* slot, int32_t* n_moves, int32_t* winner, float* score, int8_t* terr);
+/* ---- policy surprise weighting (KataGo's policySurpriseDataWeight; DESIGN.md 15, transgo_amd/policy_surprise.py) -----------------
+ * How often a position of a finished game is written to the training data.  weight = lambda in [0, 1] (0 = off, the default; KataGo
+ * uses 0.5; anything else is TG_ERR_ARG), seed = the seed of the copy draws.  For a harvested position with recorded counts c and the
+ * network's float32 policy row p for it (all in float64): c' = c with 1 -> 0, n = sum c', pi = c' / n,
+ * s = max(0, sum over c'_a > 0 of pi_a * (log pi_a - log max(p_a, FLT_MIN))), s = 0 when n == 0; for a game with T harvested
+ * positions t = 0..T-1 (plies kept out of the record do not count) and S = s_0 + s_1 + ... in that order:
+ * w_t = (1 - lambda) + lambda * T * s_t / S (1 when S == 0), k_t = floor(w_t + tg_host_cap_draw(game seed, t, seed ^ 0x50535731)
+ * / 2^24).  The resampled batch holds position t k_t times in a row (possibly 0 times); games and plies keep their order, the
+ * per-game n_moves are the sums of the k_t, every other per-game table is tg_sp_harvest's.  No part of the search changes, no
+ * game's MT19937 stream is touched, and while the weight is 0 nothing of this is launched or allocated.  The setting is context
+ * state like tg_sp_forced_playouts': not part of a snapshot (set it again after tg_sp_restore; a plan holds no state beyond the
+ * finished games, so games restored finished-but-unharvested resample identically). */
+int tg_sp_policy_surprise(tg_ctx* ctx, double weight, uint32_t seed);
+int tg_sp_policy_surprise_get(tg_ctx* ctx, double* weight, uint32_t* seed);
+/* The two-call pattern of tg_sp_finished / tg_sp_harvest.  The PLAN call works on the games the last tg_sp_play finished (it runs
+ * their plain harvest into HBM of its own) and returns n_out, the positions of the resampled batch.  prior = host rows
+ * f32[n_positions][A] in tg_sp_harvest's order, or NULL: the loaded network then runs over the harvested positions, straight from
+ * their bit-packed observations, in chunks of at most the engine's row capacity (n_games * parallel_readouts), in identity
+ * orientation whatever tg_net_set_symmetry says, past the evaluation cache (no lookup, no insert, no counter moves), into rows of
+ * its own -- a root batch tg_sp_play left pending is not disturbed, and tg_sp_stats' evals does not count these rows
+ * (tg_sp_policy_surprise_stats does).  game_seed u32[cfg.n_games]: the seed of the game in every SLOT (the finished games pick
+ * theirs).  Optional read-outs for tests and analysis, each may be NULL: surprise f64[n_positions], weight f64[n_positions], copies
+ * i32[n_positions], prior_out f32[n_positions][A] = the prior rows used.  TG_ERR_STATE while the weight is 0, and with prior ==
+ * NULL while no network is loaded; the message says which. */
+int tg_sp_policy_surprise_plan(tg_ctx* ctx, const float* prior, const uint32_t* game_seed, int32_t* n_out, double* surprise,
+                               double* weight, int32_t* copies, float* prior_out);
+/* tg_sp_harvest's argument list with the position arrays sized for n_out: the resampled batch, to host arrays or (device_out != 0)
+ * into this GPU's memory.  TG_ERR_STATE when no plan is current for the games the last tg_sp_play finished (tg_sp_play, tg_sp_reset,
+ * tg_sp_reset_from, tg_sp_restore and tg_sp_policy_surprise each end a plan). */
+int tg_sp_policy_surprise_harvest(tg_ctx* ctx, uint32_t* obs_bits, int32_t* counts, float* z, int8_t* own, uint8_t* player,
+                                  int device_out, int32_t* slot, int32_t* n_moves, int32_t* winner, float* score, int8_t* terr);
+/* Cumulative since tg_create: positions that went into plans, positions the plans put out, games planned, rows the prior forward
+ * ran (0 while every plan was given host priors).  Any pointer may be NULL. */
+int tg_sp_policy_surprise_stats(tg_ctx* ctx, uint64_t* positions_in, uint64_t* positions_out, uint64_t* games, uint64_t* rows_forwarded);
+/* HIP-event times on the context's stream, cumulative: the prior (forward, or the upload of host rows), k_psw_surprise + k_psw_plan,
+ * k_psw_gather; and the number of plans. */
+int tg_prof_read_policy_surprise(tg_ctx* ctx, double* prior_ms, double* plan_ms, double* gather_ms, int64_t* plans);
+/* k_psw_surprise and k_psw_plan on caller arrays, for any context (kernel tests, analysis of stored games): n_games games of
+ * n_moves[g] positions each, game after game; counts i32[n][A], prior f32[n][A], game_seed u32[n_games] (by game).  Outputs, each may
+ * be NULL: n_out, n_moves_out i32[n_games], surprise / weight_out f64[n], copies i32[n], src i32[min(n_out, src_cap)] = the source
+ * row of every output row. */
+int tg_policy_surprise_plan_arrays(tg_ctx* ctx, int n_games, const int32_t* n_moves, const uint32_t* game_seed, const int32_t* counts,
+                                   const float* prior, double weight, uint32_t seed, int32_t* n_out, int32_t* n_moves_out,
+                                   double* surprise, double* weight_out, int32_t* copies, int32_t* src, int src_cap);
+
 /* getScoreAndTerritory / getWinner of the current root position (self_play.py:932-937). */
 int tg_sp_final(tg_ctx* ctx, float* score /*[G]*/, float* terr /*[G][S*S]*/, int32_t* winner /*[G]*/);
 /* Aggregate counters: completed simulations, evaluated leaves, summed selection depth, RNG words drawn by tie

@@ -84,6 +84,14 @@ SIGNATURES = {
     "tg_sp_pool_stats": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint64)] * 4),
     "tg_sp_finished": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "tg_sp_harvest": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "tg_sp_policy_surprise": (ctypes.c_int, [_vp, ctypes.c_double, ctypes.c_uint32]),
+    "tg_sp_policy_surprise_get": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint32)]),
+    "tg_sp_policy_surprise_plan": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(ctypes.c_int32), _vp, _vp, _vp, _vp]),
+    "tg_sp_policy_surprise_harvest": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "tg_sp_policy_surprise_stats": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint64)] * 4),
+    "tg_prof_read_policy_surprise": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(ctypes.c_int64)]),
+    "tg_policy_surprise_plan_arrays": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_uint32,
+                                                      ctypes.POINTER(ctypes.c_int32), _vp, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "tg_sp_stats": (ctypes.c_int, [_vp] + [ctypes.POINTER(ctypes.c_uint64)] * 4 + [ctypes.POINTER(ctypes.c_int32)] * 2),
     "tg_sp_eval_cache": (ctypes.c_int, [_vp, ctypes.c_uint64]),
     "tg_sp_eval_cache_clear": (ctypes.c_int, [_vp]),

@@ -50,6 +50,11 @@ class Config:
         self.search_ownership = False            # True: every search also averages the ownership head over the positions it evaluates
                                                  # (SelfPlayEngine.root_ownership; analysis).  The search itself is unchanged; refused
                                                  # together with eval_cache_entries > 0.  policy_evaluate ignores it
+        self.policy_surprise_weight = 0.0        # > 0 (KataGo: 0.5): policy surprise weighting (transgo_amd/policy_surprise.py) -- finished
+                                                 # games are resampled on the device before they leave the harvest: a position is
+                                                 # written floor(w) or floor(w) + 1 times, w = (1 - weight) + weight * T * KL(search
+                                                 # target || raw policy) / the game's sum of those.  The search is unchanged
+        self.policy_surprise_seed = 0            # seed of the copy draws (a hash of game seed, position index and this)
         self.batch_size = 2048
         self.train_play_ratio = 7500 / 100000    # configure.py:61
         self.adjust_train_play_ratio = True
@@ -63,6 +68,8 @@ class Config:
         check_k(self.forced_playouts_k)
         from .gumbel import check_params
         check_params(self.gumbel_m, self.gumbel_c_visit, self.gumbel_c_scale)
+        from .policy_surprise import check_config as check_policy_surprise
+        check_policy_surprise(self)
         if self.gumbel_m > 0 and self.forced_playouts_k > 0:
             raise ValueError("gumbel_m > 0 and forced_playouts_k > 0: both are rules for the same root, choose one")
         if self.search_ownership and self.eval_cache_entries:

@@ -47,6 +47,7 @@ struct EngineDev {
 
 struct Net;                          // net.hip
 struct EvalCache;                    // eval_cache.hip
+struct PolicySurprise;               // policy_surprise.hip
 
 struct Engine {
     int G = 0, R = 0, rows_cap = 0;
@@ -67,6 +68,8 @@ struct Engine {
     std::vector<int32_t> fin_slot, fin_off;   // games finished by the last tg_sp_play (ascending slot) and their position offsets
     int fin_positions = 0;
     int32_t* d_fin = nullptr;        // [2][G] device copy of fin_slot / fin_off
+    uint64_t fin_seq = 0;            // bumped whenever the list of finished games is replaced (play, reset, restore): a resampling plan
+                                     // (policy_surprise.hip) is current only for the list it was made from
     DevBuf hv_obs, hv_cnt, hv_z, hv_own, hv_pl, hv_game;   // harvest staging when the caller wants host arrays
     DevBuf obs_f32;                  // float planes of the pending batch, only materialised for tg_sp_batch_obs (tests, host evaluators)
     DevBuf readout;                  // staging of tg_sp_root_children / tg_sp_pv, allocated by the first such call
@@ -101,6 +104,7 @@ struct Engine {
     int32_t* d_own_n = nullptr;      // [G]    how many simulations the sum holds
     Net* net = nullptr;
     EvalCache* cache = nullptr;      // tg_sp_eval_cache: nullptr = every pending row goes through the network (nothing else is launched)
+    PolicySurprise* psw = nullptr;   // tg_sp_policy_surprise: nullptr until the weight is first set above 0
     // HIP-event timing of the tree stage (k_collect, k_absorb) on the engine's stream, switched by tg_prof_enable
     bool tprof = false; std::vector<hipEvent_t> tev; size_t tev_used = 0; double collect_ms = 0, absorb_ms = 0; long tree_waves = 0;
     std::vector<char> tev_kind;
@@ -110,6 +114,9 @@ struct Engine {
 int eval_cache_run(tg_ctx* ctx, int rows);      // the pending batch: probe, in-batch duplicates, forward on the rest, scatter + insert
 void eval_cache_invalidate(tg_ctx* ctx);        // the evaluator changed (weights, precision, symmetry): no entry made so far may hit again
 void eval_cache_destroy(tg_ctx* ctx);
+
+// policy_surprise.hip -- policy surprise weighting
+void psw_destroy(tg_ctx* ctx);
 
 // engine.hip -- search ownership: the accumulators of the games with d_mask[g] != 0 (nullptr = every game) := 0, on
 // ctx->stream; nothing is launched while the mode is off

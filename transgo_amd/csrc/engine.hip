@@ -1683,6 +1683,7 @@ void tg_engine_destroy(tg_ctx* ctx) {
     e->obs_f32.release(); e->readout.release(); e->snap_tab.release(); e->snap_stage.release(); e->hv_obs.release(); e->hv_cnt.release(); e->hv_z.release(); e->hv_own.release(); e->hv_pl.release(); e->hv_game.release();
     for (hipEvent_t ev : e->tev) (void)hipEventDestroy(ev);
     eval_cache_destroy(ctx);
+    psw_destroy(ctx);
     tg_net_destroy(ctx);
     delete e;
     ctx->eng = nullptr;
@@ -1702,7 +1703,7 @@ int tg_sp_reset(tg_ctx* ctx, const uint32_t* seeds, const uint8_t* mask) {
     else e->rng_on_host = true;                                       // every stream is overwritten: nothing to fetch
     parallel_games(G, [&](int g) { if (!mask || mask[g]) tg_host_mt_seed(&e->h_rng[g], seeds[g]); });
     for (int g = 0; g < G; ++g) if (!mask || mask[g]) e->h_moves[g] = 0;
-    e->fin_slot.clear(); e->fin_off.clear(); e->fin_positions = 0;   // unharvested records of restarted slots are gone
+    e->fin_slot.clear(); e->fin_off.clear(); e->fin_positions = 0; ++e->fin_seq;   // unharvested records of restarted slots are gone
     TG_HIP(ctx, hipMemsetAsync(e->dev.ply_skip, 0, (size_t)G, ctx->stream));      // a move boundary: every game records again
     uint8_t* d_mask = nullptr;
     if (mask) {
@@ -1750,7 +1751,7 @@ int tg_sp_reset_from(tg_ctx* ctx, const void* states, const uint8_t* mask) {
     std::vector<uint8_t> all;
     if (mask) { TG_HIP(ctx, hipMemcpyAsync(e->d_u8, mask, G, hipMemcpyHostToDevice, ctx->stream)); d_mask = e->d_u8; }
     for (int g = 0; g < G; ++g) if (!mask || mask[g]) e->h_moves[g] = 0;
-    e->fin_slot.clear(); e->fin_off.clear(); e->fin_positions = 0;
+    e->fin_slot.clear(); e->fin_off.clear(); e->fin_positions = 0; ++e->fin_seq;
     TG_HIP(ctx, hipMemsetAsync(e->dev.ply_skip, 0, (size_t)G, ctx->stream));
     TG_HIP(ctx, hipMemsetAsync(e->d_forced, 0, (size_t)G, ctx->stream));          // (every slot is restarted or parked)
     if (e->gumbel_m > 0) TG_HIP(ctx, hipMemsetAsync(e->d_gumbel, 0, (size_t)G, ctx->stream));
@@ -2262,7 +2263,7 @@ int tg_sp_play(tg_ctx* ctx, const int32_t* actions, uint8_t* done) {
     e->n_errors = cnt[CNT_ERRORS];
     // games this call finished (a slot that was already over does not move and is not listed again), ascending slot order; a game
     // contributes the plies it recorded (k_play counted them: all of its moves unless tg_sp_begin_move_games kept some out)
-    e->fin_slot.clear(); e->fin_off.clear(); e->fin_positions = 0;
+    e->fin_slot.clear(); e->fin_off.clear(); e->fin_positions = 0; ++e->fin_seq;
     for (int g = 0; g < G; ++g)
         if (done[g] == 1 && e->h_moves[g] == prev[g] + 1) {
             const int cap = e->h_moves[g] < e->dev.hist_T ? e->h_moves[g] : e->dev.hist_T;

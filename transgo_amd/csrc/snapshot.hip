@@ -467,7 +467,7 @@ int tg_sp_restore(tg_ctx* ctx, const void* in, uint64_t bytes, int device_mem) {
     const int32_t* moves = (const int32_t*)(tab + h.sec[SEC_MOVES].off);
     const int32_t* fin = (const int32_t*)(tab + h.sec[SEC_FIN].off);
     e->h_moves.assign(moves, moves + e->G);
-    e->fin_slot.assign(fin, fin + h.n_fin); e->fin_off.assign(fin + h.n_fin, fin + 2 * h.n_fin); e->fin_positions = h.fin_positions;
+    e->fin_slot.assign(fin, fin + h.n_fin); e->fin_off.assign(fin + h.n_fin, fin + 2 * h.n_fin); e->fin_positions = h.fin_positions; ++e->fin_seq;
     e->all_reset = h.all_reset != 0; e->n_errors = h.n_errors;
     e->batch_kind = BATCH_NONE; e->batch_ready = false; e->last_rows = 0;
     e->rng_on_host = false;                                            // the device copy is the one just written

@@ -114,7 +114,7 @@ class SelfPlayEngine:
                  wu_loss=2, komi=7.5, max_step=120, encode_dim=10, net_blocks=6, net_filters=128, arena_slots=0,
                  device=0, evaluator=None, net_precision="f32", record_games=True, pool_slots=0, eval_symmetry="none",
                  symmetry_seed=0, eval_cache_entries=0, forced_playouts_k=0.0, gumbel_m=0, gumbel_c_visit=50.0,
-                 gumbel_c_scale=1.0, search_ownership=False):
+                 gumbel_c_scale=1.0, search_ownership=False, policy_surprise_weight=0.0, policy_surprise_seed=0):
         cfg = _lib.default_config()
         cfg.record_games = 1 if record_games else 0       # per-move records in HBM for tg_sp_harvest (self-play); evaluation matches need none
         cfg.net_precision = {"f32": 0, "f16": 1, "f16r": 2, "f32x3": 3}[net_precision]
@@ -147,6 +147,10 @@ class SelfPlayEngine:
         self.search_ownership = False
         if search_ownership:
             self.set_search_ownership(True)
+        self.policy_surprise_weight, self.policy_surprise_seed = 0.0, 0
+        self.policy_surprise_ms = {}                 # HIP-event milliseconds of the last resampled harvest (prior, plan, gather)
+        if policy_surprise_weight:
+            self.set_policy_surprise(policy_surprise_weight, policy_surprise_seed)
 
     def close(self):
         self.ctx.close()
@@ -298,6 +302,61 @@ class SelfPlayEngine:
         mean = np.zeros((self.G, self.S, self.S), np.float32); n = np.zeros(self.G, np.int32); lead = np.zeros(self.G, np.float32)
         self.ctx.call("tg_sp_root_ownership", _ptr(mean), _ptr(n), _ptr(lead))
         return dict(mean=mean, n=n, score_lead=lead)
+
+    # ---- policy surprise weighting (tg_sp_policy_surprise) ------------------------------------------------------
+    POLICY_SURPRISE_STATS = ("positions_in", "positions_out", "games", "rows_forwarded")
+
+    def set_policy_surprise(self, weight, seed=0):
+        """weight > 0 (KataGo: 0.5): harvest() returns the finished games resampled on the device -- a position is written
+        floor(w) or floor(w) + 1 times, w = (1 - weight) + weight * T * KL(search target || raw network policy) / the game's sum of
+        those (transgo_amd.policy_surprise holds the definition).  0.0 = off: harvest() is tg_sp_harvest as ever.  No part of the
+        search changes.  Context state: a restored snapshot does not carry it."""
+        from types import SimpleNamespace
+        from . import policy_surprise as _psw
+        w, s = _psw.check_config(SimpleNamespace(policy_surprise_weight=weight, policy_surprise_seed=seed))
+        self.ctx.call("tg_sp_policy_surprise", ctypes.c_double(w), s)
+        self.policy_surprise_weight, self.policy_surprise_seed = w, s
+
+    def get_policy_surprise(self):
+        w, s = ctypes.c_double(), ctypes.c_uint32()
+        self.ctx.call("tg_sp_policy_surprise_get", ctypes.byref(w), ctypes.byref(s))
+        return float(w.value), int(s.value)
+
+    def policy_surprise_stats(self):
+        """tg_sp_policy_surprise_stats as a dict (POLICY_SURPRISE_STATS), plus the cumulative HIP-event milliseconds of the three
+        stages (prior_ms, plan_ms, gather_ms) and the number of plans."""
+        v = [ctypes.c_uint64() for _ in self.POLICY_SURPRISE_STATS]
+        self.ctx.call("tg_sp_policy_surprise_stats", *[ctypes.byref(x) for x in v])
+        out = {k: int(x.value) for k, x in zip(self.POLICY_SURPRISE_STATS, v)}
+        ms = [ctypes.c_double() for _ in range(3)]; n = ctypes.c_int64()
+        self.ctx.call("tg_prof_read_policy_surprise", *[ctypes.byref(x) for x in ms], ctypes.byref(n))
+        out.update(prior_ms=ms[0].value, plan_ms=ms[1].value, gather_ms=ms[2].value, plans=int(n.value))
+        return out
+
+    def policy_surprise_plan(self, seeds, prior=None, readout=False):
+        """tg_sp_policy_surprise_plan for the games the last play() finished: seeds uint32[G] by slot, prior float32 [n, A] host rows
+        or None (the loaded network runs).  Returns n_out, or with readout=True a dict of n_out, surprise, weight, copies and the
+        prior rows used."""
+        ng, npos = ctypes.c_int32(), ctypes.c_int32()
+        self.ctx.call("tg_sp_finished", ctypes.byref(ng), ctypes.byref(npos))
+        npos = npos.value
+        seeds = np.ascontiguousarray(seeds, np.uint32)
+        assert seeds.shape == (self.G,), "seeds: one per slot"
+        if prior is not None:
+            prior = np.ascontiguousarray(prior, np.float32)
+            assert prior.shape == (npos, self.A), (prior.shape, (npos, self.A))
+            if npos == 0:
+                prior = np.zeros((1, self.A), np.float32)              # no rows to read, but not the NULL that asks for the network
+        n_out = ctypes.c_int32()
+        if not readout:
+            self.ctx.call("tg_sp_policy_surprise_plan", _ptr(prior), _ptr(seeds), ctypes.byref(n_out), None, None, None, None)
+            return n_out.value
+        r = dict(surprise=np.zeros(npos, np.float64), weight=np.zeros(npos, np.float64), copies=np.zeros(npos, np.int32),
+                 prior=np.zeros((npos, self.A), np.float32))
+        self.ctx.call("tg_sp_policy_surprise_plan", _ptr(prior), _ptr(seeds), ctypes.byref(n_out), _ptr(r["surprise"]),
+                      _ptr(r["weight"]), _ptr(r["copies"]), _ptr(r["prior"]))
+        r["n_out"] = n_out.value
+        return r
 
     # ---- evaluation of the pending batch --------------------------------------------------------------------------------
     def _evaluate(self, rows=None):
@@ -487,13 +546,31 @@ class SelfPlayEngine:
 
     def harvest(self, device=False, seeds=None):
         """The games the last play() finished, as one position-major batch (transgo_amd.records.Harvest), or None.
-        device=True: the batch is a torch uint8 tensor in this GPU's memory and only the per-game tables cross PCIe."""
+        device=True: the batch is a torch uint8 tensor in this GPU's memory and only the per-game tables cross PCIe.
+        While policy_surprise_weight > 0 the batch is the resampled one (set_policy_surprise) and `seeds` is required."""
         from . import records
         ng, npos = ctypes.c_int32(), ctypes.c_int32()
         self.ctx.call("tg_sp_finished", ctypes.byref(ng), ctypes.byref(npos))
         ng, npos = ng.value, npos.value
         if ng == 0:
             return None
+        fn = "tg_sp_harvest"
+        if self.policy_surprise_weight > 0.0:
+            # policy surprise weighting: the batch is resampled on the device before it leaves; everything behind this call keeps
+            # seeing a position batch, only with other per-game lengths
+            if seeds is None:
+                raise ValueError("policy surprise weighting is on: harvest() needs the games' seeds (seeds=, one per slot) for the copy draws")
+            prior = None
+            if self.evaluator is not None and npos > 0:
+                # a host evaluator stands in for the network: its policy rows for the harvested positions, identity orientation
+                plain = records.Harvest(self.S, self.C, ng, npos, np.zeros(records.layout(self.S, self.C, ng, npos)[1], np.uint8))
+                self.ctx.call("tg_sp_harvest", plain.ptr("obs_bits"), plain.ptr("counts"), plain.ptr("z"), plain.ptr("own"),
+                              plain.ptr("player"), 0, None, None, None, None, None)
+                prior = np.ascontiguousarray(self.evaluator(plain.observations())[0], np.float32)
+            elif self.evaluator is not None:
+                prior = np.zeros((0, self.A), np.float32)
+            npos = self.policy_surprise_plan(seeds, prior)
+            fn = "tg_sp_policy_surprise_harvest"
         sec, total = records.layout(self.S, self.C, ng, npos)
         hdr = records.header_bytes(self.S, self.C, ng)
         if device:
@@ -505,7 +582,7 @@ class SelfPlayEngine:
             buf = np.zeros(total, np.uint8)
         h = records.Harvest(self.S, self.C, ng, npos, buf)
         t = host if device else h
-        self.ctx.call("tg_sp_harvest", h.ptr("obs_bits"), h.ptr("counts"), h.ptr("z"), h.ptr("own"), h.ptr("player"),
+        self.ctx.call(fn, h.ptr("obs_bits"), h.ptr("counts"), h.ptr("z"), h.ptr("own"), h.ptr("player"),
                       1 if device else 0, t.ptr("slot"), t.ptr("n_moves"), t.ptr("winner"), t.ptr("score"), t.ptr("terr"))
         if seeds is not None:
             t.view("seed")[:] = np.asarray(seeds, np.uint32)[t.view("slot")]

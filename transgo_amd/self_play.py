@@ -14,6 +14,7 @@ import numpy as np
 from .engine import SelfPlayEngine
 from . import model as _model
 from . import playout_cap
+from . import policy_surprise
 
 
 def _call(method, *args):
@@ -102,7 +103,9 @@ class BatchedSelfPlay:
             forced_playouts_k=getattr(config, "forced_playouts_k", 0.0),
             gumbel_m=getattr(config, "gumbel_m", 0), gumbel_c_visit=getattr(config, "gumbel_c_visit", 50.0),
             gumbel_c_scale=getattr(config, "gumbel_c_scale", 1.0),
-            search_ownership=bool(getattr(config, "search_ownership", False)))
+            search_ownership=bool(getattr(config, "search_ownership", False)),
+            policy_surprise_weight=policy_surprise.check_config(config)[0],
+            policy_surprise_seed=getattr(config, "policy_surprise_seed", 0))
         self.seed_fn = seed_fn
         self.games_started = np.zeros(n_games, np.int64)
         self.seeds = np.zeros(n_games, np.uint32)          # seed of the game now running in each slot
@@ -267,6 +270,7 @@ class BatchedSelfPlay:
         self.engine.set_forced_playouts(getattr(self.config, "forced_playouts_k", 0.0))      # context state, not part of a snapshot
         self.engine.set_gumbel(getattr(self.config, "gumbel_m", 0), getattr(self.config, "gumbel_c_visit", 50.0),
                                getattr(self.config, "gumbel_c_scale", 1.0))
+        self.engine.set_policy_surprise(getattr(self.config, "policy_surprise_weight", 0.0), getattr(self.config, "policy_surprise_seed", 0))
         self.games_started = np.asarray(state["games_started"], np.int64)
         self.seeds = np.asarray(state["seeds"], np.uint32)
         self.moves_played, self.games_finished = int(state["moves_played"]), int(state["games_finished"])
