@@ -107,6 +107,16 @@ int tg_env_step(tg_ctx* ctx, const void* in, void* out, const int32_t* actions, 
 int tg_env_query(tg_ctx* ctx, const void* states, int n, uint8_t* legal, uint8_t* noeye, float* obs, float* score,
                  float* terr, int32_t* player, int32_t* step, uint8_t* terminated);
 
+/* Pass-alive groups and territory (Benson's algorithm; transgo_amd/pass_alive.py is the definition).  Per state:
+ *   status  i8[n][S*S]  +2 pass-alive Black stone, +1 Black pass-alive territory (an empty point or a dead White stone), -2 / -1
+ *                       White likewise, 0 everything else.
+ *   settled u8[n]       1 if no point has status 0.
+ *   owner   i8[n][S*S]  the pass-alive-aware area: the status' colour where it is not 0, Tromp-Taylor elsewhere (+1 / -1 / 0 dame).
+ *   score   f32[n]      #Black - #White of owner, minus komi; Black wins iff score > 0.
+ * settled, score and owner may be NULL.  States, outputs and errors follow tg_env_query. */
+int tg_env_pass_alive(tg_ctx* ctx, const void* states, int n, int8_t* status /*[n][S*S]*/, uint8_t* settled /*[n] or NULL*/,
+                      float* score /*[n] or NULL*/, int8_t* owner /*[n][S*S] or NULL*/);
+
 /* Show (go_env.h:63): prints the board of one state to stdout. */
 int tg_env_show(tg_ctx* ctx, const void* state);
 
@@ -303,6 +313,25 @@ int tg_sp_set_eval_own(tg_ctx* ctx, const float* policy /*[n_rows][A]*/, const f
  * sign of tg_sp_final's score.  A read-out like tg_sp_root_children: nothing changes, legal at any move boundary.  TG_ERR_STATE
  * before the first tg_sp_reset and while the mode is off.  Any pointer may be NULL. */
 int tg_sp_root_ownership(tg_ctx* ctx, float* mean /*[G][S*S] or NULL*/, int32_t* n /*[G] or NULL*/, float* score_lead /*[G] or NULL*/);
+
+/* Pass-alive end.  Context state, off by default.  While it is on:
+ *   - after tg_sp_play has advanced the games, every game that is still running and whose new root is settled (tg_env_pass_alive)
+ *     ends there: its root state is terminated, no evaluation of that root is requested, done[g] = 1 and the game is listed by
+ *     tg_sp_finished with its recorded plies, exactly like a game that ended by double pass;
+ *   - tg_sp_reset_from treats a settled state like a terminated one;
+ *   - tg_sp_harvest (z, ownership target, winner, score, territory) and tg_sp_final score with the pass-alive-aware area, for every
+ *     game, however it ended.
+ * The search inside the tree is unchanged (leaves keep the plain rules), so visits and moves up to the ply of settlement are those
+ * of the mode off.  While it is off nothing of this is launched.  Neither the switch nor the counters are part of a snapshot: set
+ * the mode before tg_sp_restore.  TG_ERR_STATE while a leaf batch is pending. */
+int tg_sp_pass_alive(tg_ctx* ctx, int on);
+int tg_sp_pass_alive_get(tg_ctx* ctx, int* on);
+/* Since the mode was first turned on: games ended by settlement, and the sum of the plies they had played. */
+int tg_sp_pass_alive_stats(tg_ctx* ctx, uint64_t* games_settled, uint64_t* plies_at_settlement_sum);
+/* tg_env_pass_alive's status and settled for the games' current roots.  A read-out like tg_sp_root_children: nothing changes, the
+ * mode need not be on.  TG_ERR_STATE before the first tg_sp_reset.  Either pointer may be NULL.  A game parked in error without a root
+ * block (tg_sp_game_errors) reads as an empty board: status 0 everywhere, not settled. */
+int tg_sp_root_pass_alive(tg_ctx* ctx, int8_t* status /*[G][S*S] or NULL*/, uint8_t* settled /*[G] or NULL*/);
 
 /* One random_sample() from each game's stream: the draw inside np.random.choice(A, p=) (self_play.py:683). */
 int tg_sp_draw_uniform(tg_ctx* ctx, double* u /*[G]*/, const uint8_t* mask);

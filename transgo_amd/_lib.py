@@ -73,6 +73,11 @@ SIGNATURES = {
     "tg_sp_search_ownership_get": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
     "tg_sp_set_eval_own": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int32]),
     "tg_sp_root_ownership": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "tg_env_pass_alive": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _u8p, _f32p, _vp]),
+    "tg_sp_pass_alive": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "tg_sp_pass_alive_get": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
+    "tg_sp_pass_alive_stats": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "tg_sp_root_pass_alive": (ctypes.c_int, [_vp, _vp, _vp]),
     "tg_sp_draw_uniform": (ctypes.c_int, [_vp, _vp, _vp]),
     "tg_sp_rng_state": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(TgMt19937)]),
     "tg_sp_rng_get": (ctypes.c_int, [_vp, _vp]),

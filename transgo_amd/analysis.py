@@ -19,7 +19,7 @@ def vertex(action, board_size):
     return f"{_COLUMNS[action % S]}{S - action // S}"
 
 
-def analyse(engine, states, num_simulation=0, depth=16, symmetry=None, eval_cache_entries=None, ownership=False):
+def analyse(engine, states, num_simulation=0, depth=16, symmetry=None, eval_cache_entries=None, ownership=False, pass_alive=False):
     """Search every position of `states` ([N, state_size] uint8 blobs of transgo_amd.environment.GoEnv) in evaluation mode -- a
     fresh root, no root noise, as select_action's prologue (self_play.py:689-700) -- and read the trees out.  The engine's games
     are re-rooted (`reset_from`), so whatever they held is gone; the engine must have been `reset` once before (that seeds the
@@ -42,7 +42,21 @@ def analyse(engine, states, num_simulation=0, depth=16, symmetry=None, eval_cach
       ownership_evals  int            how many evaluations that mean rests on (0: the map is all zero)
       score_lead       float          float32 sum of the map in point order - komi: black's lead as the search sees it
     The engine must then have no evaluation cache (it stores no ownership): asking for both raises ValueError.
+    pass_alive: True adds what is settled by proof and not by opinion (tg_env_pass_alive; transgo_amd/pass_alive.py) to every record:
+      pass_alive        int8[S, S]  +2 / -2 pass-alive black / white stone, +1 / -1 pass-alive territory, 0 everything else
+      settled           bool        no point has status 0
+      pass_alive_score  float       the pass-alive-aware area (status where it is not 0, Tromp-Taylor elsewhere) - komi
     """
+    if pass_alive:
+        recs = analyse(engine, states, num_simulation, depth, symmetry, eval_cache_entries, ownership)
+        st = np.ascontiguousarray(states, np.uint8)
+        N, S = st.shape[0], engine.S
+        status = np.zeros((N, S * S), np.int8); settled = np.zeros(N, np.uint8); score = np.zeros(N, np.float32)
+        if N:
+            engine.ctx.call("tg_env_pass_alive", st.ctypes.data, N, status.ctypes.data, settled.ctypes.data, score.ctypes.data, None)
+        for i, r in enumerate(recs):
+            r.update(pass_alive=status[i].reshape(S, S).copy(), settled=bool(settled[i]), pass_alive_score=float(score[i]))
+        return recs
     states = np.ascontiguousarray(states, np.uint8)
     if states.ndim != 2:
         raise ValueError("states must be [N, state_size]")
@@ -170,19 +184,26 @@ def format_analysis(record, board_size, top=5, ownership=None):
     action) with its vertex, visits, q, prior and its line -- the principal variation for the move that heads it, the move alone
     for the others.  A q that is NaN (never visited) prints as '-'.  `ownership`: a `playout_ownership` record of the same
     position, printed underneath (format_ownership).  A record that carries its own search ownership (analyse(..., ownership=True))
-    prints that board too."""
+    prints that board too.  A record with a pass-alive status (analyse(..., pass_alive=True)) gains a column `pa` -- the status of
+    the candidate's point: B / W a pass-alive stone, b / w pass-alive territory, . unsettled -- and a line with the settled flag and
+    the pass-alive-aware score."""
+    status = np.asarray(record["pass_alive"]).reshape(-1) if "pass_alive" in record else None
+    mark = lambda a: "" if status is None else f"{'-' if a >= len(status) else {2: 'B', 1: 'b', 0: '.', -1: 'w', -2: 'W'}[int(status[a])]:>4}"
     visits, prior, q = np.asarray(record["visits"]), np.asarray(record["prior"]), np.asarray(record["q"])
     legal = np.asarray(record["legal"]) if "legal" in record else (visits > 0) | (prior > 0)
     cand = sorted(np.flatnonzero(legal), key=lambda a: (-int(visits[a]), int(a)))[:max(int(top), 0)]
     pv = list(record.get("pv", []))
     rv = record.get("root_value", float("nan"))
     lines = [f"root value {'-' if np.isnan(rv) else format(rv, '+.3f')}   visits {int(visits.sum())}",
-             f"{'move':<5}{'visits':>8}{'q':>8}{'prior':>8}  pv"]
+             f"{'move':<5}{'visits':>8}{'q':>8}{'prior':>8}{'' if status is None else '  pa'}  pv"]
     for a in cand:
         qs = "-" if np.isnan(q[a]) else format(float(q[a]), "+.3f")
         line = pv if pv and pv[0] == a else [a]
-        lines.append(f"{vertex(a, board_size):<5}{int(visits[a]):>8}{qs:>8}{float(prior[a]):>8.4f}  "
+        lines.append(f"{vertex(a, board_size):<5}{int(visits[a]):>8}{qs:>8}{float(prior[a]):>8.4f}{mark(a)}  "
                      + " ".join(vertex(m, board_size) for m in line))
+    if status is not None:
+        lines.append(f"pass-alive: {'settled' if record['settled'] else 'not settled'}, {int((status != 0).sum())} of {len(status)} points decided, "
+                     f"score {record['pass_alive_score']:+.1f}")
     if "ownership" in record:
         lines.append(format_ownership(record, board_size))
     if ownership is not None:

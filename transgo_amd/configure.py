@@ -55,6 +55,10 @@ class Config:
                                                  # written floor(w) or floor(w) + 1 times, w = (1 - weight) + weight * T * KL(search
                                                  # target || raw policy) / the game's sum of those.  The search is unchanged
         self.policy_surprise_seed = 0            # seed of the copy draws (a hash of game seed, position index and this)
+        self.pass_alive_end = False              # True: a self-play game ends as soon as every point of its board is a pass-alive stone or
+                                                 # pass-alive territory (Benson's algorithm, transgo_amd/pass_alive.py), and finished
+                                                 # games are scored with the pass-alive-aware area.  The search is unchanged; only False
+                                                 # keeps parity with the reference
         self.batch_size = 2048
         self.train_play_ratio = 7500 / 100000    # configure.py:61
         self.adjust_train_play_ratio = True

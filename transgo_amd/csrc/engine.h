@@ -105,6 +105,11 @@ struct Engine {
     Net* net = nullptr;
     EvalCache* cache = nullptr;      // tg_sp_eval_cache: nullptr = every pending row goes through the network (nothing else is launched)
     PolicySurprise* psw = nullptr;   // tg_sp_policy_surprise: nullptr until the weight is first set above 0
+    // Pass-alive end: context state, off by default -- only while it is on is k_pa_end launched behind k_play / k_reset
+    // and do tg_sp_harvest / tg_sp_final score with the pass-alive-aware area (pass_alive.hip).  Not part of a snapshot.
+    bool pa_on = false;
+    unsigned long long* d_pa_stat = nullptr;   // [2]  games ended by settlement, sum of their plies (allocated when the mode is first set)
+    DevBuf pa_buf;                   // staging of tg_sp_root_pass_alive
     // HIP-event timing of the tree stage (k_collect, k_absorb) on the engine's stream, switched by tg_prof_enable
     bool tprof = false; std::vector<hipEvent_t> tev; size_t tev_used = 0; double collect_ms = 0, absorb_ms = 0; long tree_waves = 0;
     std::vector<char> tev_kind;
@@ -117,6 +122,15 @@ void eval_cache_destroy(tg_ctx* ctx);
 
 // policy_surprise.hip -- policy surprise weighting
 void psw_destroy(tg_ctx* ctx);
+
+// pass_alive.hip -- pass-alive end.  pa_end_games: nothing is launched while the mode is off; d_mask = the games to look
+// at (nullptr = every game), d_done / d_rec = k_play's outputs (nullptr behind a reset).  pa_harvest / pa_final: k_harvest / k_final
+// with the pass-alive-aware area, same arguments.  All on ctx->stream.
+int pa_end_games(tg_ctx* ctx, const uint8_t* d_mask, uint8_t* d_done, int32_t* d_rec);
+int pa_harvest(tg_ctx* ctx, int nf, const int32_t* slot, const int32_t* off, uint32_t* o_obs, int32_t* o_cnt, float* o_z, int8_t* o_own,
+               uint8_t* o_pl, int32_t* o_winner, float* o_score, int8_t* o_terr);
+int pa_final(tg_ctx* ctx, float* d_score, float* d_terr, int32_t* d_winner);
+void pa_destroy(tg_ctx* ctx);
 
 // engine.hip -- search ownership: the accumulators of the games with d_mask[g] != 0 (nullptr = every game) := 0, on
 // ctx->stream; nothing is launched while the mode is off

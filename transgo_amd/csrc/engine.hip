@@ -1269,6 +1269,7 @@ __global__ __launch_bounds__(64) void k_play_gumbel(EngineDev d, const int32_t* 
 // winner else -1 (:931-934) and the territory seen from the mover (:938-940), at the game's offset of a position-major batch
 // -- exactly the arrays tg_replay_append stores.  Plies marked kPlySkip (fast searches of playout cap randomization) are left
 // out: the game's positions are its unmarked plies, dense, in ply order; z and ownership come from the final position all the same.
+// (pass_alive.hip holds a twin, k_harvest_pa, that differs in the scorer only: a change to the record's layout goes into both.)
 template <int S>
 __global__ __launch_bounds__(64) void k_harvest(EngineDev d, const int32_t* slot, const int32_t* off, uint32_t* o_obs,
                                                 int32_t* o_cnt, float* o_z, int8_t* o_own, uint8_t* o_pl, int32_t* o_winner,
@@ -1684,6 +1685,7 @@ void tg_engine_destroy(tg_ctx* ctx) {
     for (hipEvent_t ev : e->tev) (void)hipEventDestroy(ev);
     eval_cache_destroy(ctx);
     psw_destroy(ctx);
+    pa_destroy(ctx);
     tg_net_destroy(ctx);
     delete e;
     ctx->eng = nullptr;
@@ -1763,6 +1765,7 @@ int tg_sp_reset_from(tg_ctx* ctx, const void* states, const uint8_t* mask) {
     if (ctx->S == 9) hipLaunchKernelGGL(k_reset<9>, dim3(G), dim3(64), 0, ctx->stream, e->dev, (const uint8_t*)d_mask, (const BoardState<9>*)ctx->env_in.p);
     else hipLaunchKernelGGL(k_reset<19>, dim3(G), dim3(64), 0, ctx->stream, e->dev, (const uint8_t*)d_mask, (const BoardState<19>*)ctx->env_in.p);
     TG_HIP(ctx, hipGetLastError());
+    { int rc = pa_end_games(ctx, d_mask, nullptr, nullptr); if (rc) return rc; }   // pass-alive end: a settled position is a finished game
     hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, ctx->stream, e->dev, e->R, 0);
     TG_HIP(ctx, hipGetLastError());
     int32_t cnt[CNT_N];
@@ -2250,6 +2253,7 @@ int tg_sp_play(tg_ctx* ctx, const int32_t* actions, uint8_t* done) {
     else if (e->gumbel_m > 0) TG_LAUNCH(ctx, k_play_gumbel, G, e->dev, (const int32_t*)d_act, e->d_u8, d_moves, d_rec, e->d_gumbel,
                                         (const int32_t*)e->d_gumbel_target, e->d_gumbel_staged);
     else TG_LAUNCH(ctx, k_play, G, e->dev, (const int32_t*)d_act, e->d_u8, d_moves, d_rec);
+    { int rc = pa_end_games(ctx, nullptr, e->d_u8, d_rec); if (rc) return rc; }        // pass-alive end: games whose new root is settled end here
     hipLaunchKernelGGL(k_pool_publish, dim3(1), dim3(1), 0, ctx->stream, e->dev);      // the old trees' chunks are poppable from here on
     hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, ctx->stream, e->dev, e->R, 0);
     TG_HIP(ctx, hipGetLastError());
@@ -2302,8 +2306,12 @@ int tg_sp_harvest(tg_ctx* ctx, uint32_t* obs_bits, int32_t* counts, float* z, in
     // per-game results: winner i32[nf] | score f32[nf] | terr i8[nf][P]
     if (e->hv_game.reserve((size_t)nf * (8 + P))) TG_FAIL(ctx, TG_ERR_HIP, "hipMalloc failed");
     int32_t* d_w = (int32_t*)e->hv_game.p; float* d_s = (float*)(d_w + nf); int8_t* d_t = (int8_t*)(d_s + nf);
-    TG_LAUNCH(ctx, k_harvest, nf, e->dev, (const int32_t*)e->d_fin, (const int32_t*)(e->d_fin + e->G), d_obs, d_cnt, d_z, d_own,
-              d_pl, d_w, d_s, d_t);
+    if (e->pa_on) {
+        int rc = pa_harvest(ctx, nf, (const int32_t*)e->d_fin, (const int32_t*)(e->d_fin + e->G), d_obs, d_cnt, d_z, d_own, d_pl, d_w, d_s, d_t);
+        if (rc) return rc;
+    } else
+        TG_LAUNCH(ctx, k_harvest, nf, e->dev, (const int32_t*)e->d_fin, (const int32_t*)(e->d_fin + e->G), d_obs, d_cnt, d_z, d_own,
+                  d_pl, d_w, d_s, d_t);
     if (!device_out && np > 0) {
         TG_HIP(ctx, hipMemcpyAsync(obs_bits, d_obs, sizeof(uint32_t) * (size_t)np * W, hipMemcpyDeviceToHost, ctx->stream));
         TG_HIP(ctx, hipMemcpyAsync(counts, d_cnt, sizeof(int32_t) * (size_t)np * A, hipMemcpyDeviceToHost, ctx->stream));
@@ -2355,7 +2363,8 @@ int tg_sp_final(tg_ctx* ctx, float* score, float* terr, int32_t* winner) {
     Engine* e = ctx->eng;
     const int G = e->G, P = ctx->P;
     float* d_score = e->d_f32; float* d_terr = d_score + G; int32_t* d_w = e->d_i32;
-    TG_LAUNCH(ctx, k_final, G, e->dev, d_score, terr ? d_terr : nullptr, d_w);
+    if (e->pa_on) { int rc = pa_final(ctx, d_score, terr ? d_terr : nullptr, d_w); if (rc) return rc; }
+    else TG_LAUNCH(ctx, k_final, G, e->dev, d_score, terr ? d_terr : nullptr, d_w);
     if (score) TG_HIP(ctx, hipMemcpyAsync(score, d_score, sizeof(float) * G, hipMemcpyDeviceToHost, ctx->stream));
     if (terr) TG_HIP(ctx, hipMemcpyAsync(terr, d_terr, sizeof(float) * (size_t)G * P, hipMemcpyDeviceToHost, ctx->stream));
     if (winner) TG_HIP(ctx, hipMemcpyAsync(winner, d_w, sizeof(int32_t) * G, hipMemcpyDeviceToHost, ctx->stream));

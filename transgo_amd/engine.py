@@ -114,7 +114,8 @@ class SelfPlayEngine:
                  wu_loss=2, komi=7.5, max_step=120, encode_dim=10, net_blocks=6, net_filters=128, arena_slots=0,
                  device=0, evaluator=None, net_precision="f32", record_games=True, pool_slots=0, eval_symmetry="none",
                  symmetry_seed=0, eval_cache_entries=0, forced_playouts_k=0.0, gumbel_m=0, gumbel_c_visit=50.0,
-                 gumbel_c_scale=1.0, search_ownership=False, policy_surprise_weight=0.0, policy_surprise_seed=0):
+                 gumbel_c_scale=1.0, search_ownership=False, policy_surprise_weight=0.0, policy_surprise_seed=0,
+                 pass_alive_end=False):
         cfg = _lib.default_config()
         cfg.record_games = 1 if record_games else 0       # per-move records in HBM for tg_sp_harvest (self-play); evaluation matches need none
         cfg.net_precision = {"f32": 0, "f16": 1, "f16r": 2, "f32x3": 3}[net_precision]
@@ -151,6 +152,9 @@ class SelfPlayEngine:
         self.policy_surprise_ms = {}                 # HIP-event milliseconds of the last resampled harvest (prior, plan, gather)
         if policy_surprise_weight:
             self.set_policy_surprise(policy_surprise_weight, policy_surprise_seed)
+        self.pass_alive_end = False
+        if pass_alive_end:
+            self.set_pass_alive_end(True)
 
     def close(self):
         self.ctx.close()
@@ -303,6 +307,33 @@ class SelfPlayEngine:
         self.ctx.call("tg_sp_root_ownership", _ptr(mean), _ptr(n), _ptr(lead))
         return dict(mean=mean, n=n, score_lead=lead)
 
+    # ---- pass-alive end (tg_sp_pass_alive) ------------------------------------------------------------------------
+    def set_pass_alive_end(self, on):
+        """on: a game whose new root is settled after play() -- every point a pass-alive stone or pass-alive territory
+        (transgo_amd/pass_alive.py) -- ends there like a game that ended by double pass, reset_from treats a settled position as a
+        finished game, and harvest() / final() score every game with the pass-alive-aware area.  The search itself is unchanged.
+        Off is the default.  Context state: a snapshot does not carry the switch, set it before restoring."""
+        self.ctx.call("tg_sp_pass_alive", 1 if on else 0)
+        self.pass_alive_end = bool(on)
+
+    def get_pass_alive_end(self):
+        on = ctypes.c_int()
+        self.ctx.call("tg_sp_pass_alive_get", ctypes.byref(on))
+        return bool(on.value)
+
+    def pass_alive_stats(self):
+        """-> dict(games_settled, plies_at_settlement_sum) since the mode was first turned on."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self.ctx.call("tg_sp_pass_alive_stats", ctypes.byref(a), ctypes.byref(b))
+        return dict(games_settled=int(a.value), plies_at_settlement_sum=int(b.value))
+
+    def root_pass_alive(self):
+        """tg_sp_root_pass_alive: "status" int8 [G, P] and "settled" bool [G] of the games' current roots (a read-out; the mode
+        need not be on)."""
+        status = np.zeros((self.G, self.P), np.int8); settled = np.zeros(self.G, np.uint8)
+        self.ctx.call("tg_sp_root_pass_alive", _ptr(status), _ptr(settled))
+        return dict(status=status, settled=settled.astype(bool))
+
     # ---- policy surprise weighting (tg_sp_policy_surprise; DESIGN.md 15) ------------------------------------------------------
     POLICY_SURPRISE_STATS = ("positions_in", "positions_out", "games", "rows_forwarded")
 
@@ -410,6 +441,8 @@ class SelfPlayEngine:
         self._evaluate()
         self.ctx.call("tg_sp_expand_roots")
         self.finished = np.zeros(self.G, bool) if mask is None else ~np.asarray(mask, bool)
+        if self.pass_alive_end:
+            self.finished |= self.root_pass_alive()["settled"]        # pass-alive end: a settled position is a finished game
 
     def root_states(self):
         st = np.zeros((self.G, self.ctx.state_size), np.uint8)

@@ -67,6 +67,16 @@ class GoEnv:
                       g("player"), g("step"), g("terminated"))
         return r
 
+    def pass_alive_batch(self, states):
+        """Pass-alive groups and territory of n states in one launch (tg_env_pass_alive; transgo_amd/pass_alive.py is the definition)
+        -> dict(status int8[n][P], settled bool[n], score float32[n], owner int8[n][P]); score and owner are the pass-alive-aware area."""
+        states = np.ascontiguousarray(states, np.uint8)
+        n = states.shape[0]
+        status = np.zeros((n, self.P), np.int8); owner = np.zeros((n, self.P), np.int8)
+        settled = np.zeros(n, np.uint8); score = np.zeros(n, np.float32)
+        self.ctx.call("tg_env_pass_alive", _ptr(states), n, _ptr(status), _ptr(settled), _ptr(score), _ptr(owner))
+        return dict(status=status, settled=settled.astype(bool), score=score, owner=owner)
+
     ROLLOUT_POLICIES = {"noeye": 0, "legal": 1}               # TG_ROLLOUT_NOEYE / TG_ROLLOUT_LEGAL
 
     def seed_streams(self, seeds):

@@ -105,7 +105,8 @@ class BatchedSelfPlay:
             gumbel_c_scale=getattr(config, "gumbel_c_scale", 1.0),
             search_ownership=bool(getattr(config, "search_ownership", False)),
             policy_surprise_weight=policy_surprise.check_config(config)[0],
-            policy_surprise_seed=getattr(config, "policy_surprise_seed", 0))
+            policy_surprise_seed=getattr(config, "policy_surprise_seed", 0),
+            pass_alive_end=bool(getattr(config, "pass_alive_end", False)))
         self.seed_fn = seed_fn
         self.games_started = np.zeros(n_games, np.int64)
         self.seeds = np.zeros(n_games, np.uint32)          # seed of the game now running in each slot
@@ -271,6 +272,7 @@ class BatchedSelfPlay:
         self.engine.set_gumbel(getattr(self.config, "gumbel_m", 0), getattr(self.config, "gumbel_c_visit", 50.0),
                                getattr(self.config, "gumbel_c_scale", 1.0))
         self.engine.set_policy_surprise(getattr(self.config, "policy_surprise_weight", 0.0), getattr(self.config, "policy_surprise_seed", 0))
+        self.engine.set_pass_alive_end(bool(getattr(self.config, "pass_alive_end", False)))
         self.games_started = np.asarray(state["games_started"], np.int64)
         self.seeds = np.asarray(state["seeds"], np.uint32)
         self.moves_played, self.games_finished = int(state["moves_played"]), int(state["games_finished"])
@@ -409,6 +411,13 @@ class GroupedSelfPlay:
 
     def get_search_ownership(self):
         return self.parts[0].engine.get_search_ownership()
+
+    # pass-alive end (SelfPlayEngine.set_pass_alive_end): the switch reaches every group
+    def set_pass_alive_end(self, on):
+        self._each(lambda p: p.engine.set_pass_alive_end(on))
+
+    def get_pass_alive_end(self):
+        return self.parts[0].engine.get_pass_alive_end()
 
     def root_ownership(self):
         parts = self._each(lambda p: p.engine.root_ownership())
